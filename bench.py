@@ -9,12 +9,15 @@ Workload at N GPUs: BASELINE configs[1] (GPR + RBF, N=8192, d=16, fp64, syntheti
 the restart search (configs[3]) sharded one stream of fits per GPU; RCCL is used only for the
 broadcast of (x, y) before and the all-gather of results after the timed region ("weak" scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  The K-step window is timed `--windows` times (each bracketed by barrier +
-synchronize); `value` is K / (median window time), every window is listed.  `roofline` is for the dominant
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times ONE window of exactly K steps (bracketed by
+barrier + synchronize), optionally writes the last step's outputs (--dump-outputs) and prints the headline:
+`value` = K / window time, `ms_per_step` = window time / K.  Everything below is measured only with --full,
+which also times the K-step window `--windows` times (default 5; `value` is K / median window time, every
+window is listed).  `roofline` is for the dominant
 kernel (gemm_f64_kernel, the fp64 MFMA GEMM behind the Cholesky trailing updates, the panel solves, the
 fused triangular inverse and E E'): ALGORITHMIC flops of a fit that run in it (N^3: Cholesky N^3/3 +
 inverse N^3/3 + E E' N^3/3) / its launches / their average duration, measured with HIP events on the
@@ -25,7 +28,7 @@ reference-faithful CPU path (scipy cdist + LAPACK dpotrf + general-LU solve_chol
 per hyper, call-for-call what pyGPs does) on this host's cores: ONE full fit at the benchmark size.
 
 Schema notes.  `per_rank_fits_per_s` lists every rank's own rate, `value` the aggregate (the slowest rank's window).  The
-collective extras (`cfg4_restarts_N8192`, `sharded_fit`) run after the timed region behind a 300 s watchdog:
+collective extras of --full (`cfg4_restarts_N8192`, `sharded_fit`) run after the timed region behind a 300 s watchdog:
 `collective_extras_ok` is false -- and `collective_extras_error` says why -- when they did not finish; the line (and rc 0)
 still goes out so that the headline survives a stall on hardware the collective path has never seen.  With `--gpus N > 1`
 and no launcher environment the script re-executes itself under `python -m torch.distributed.run --nproc-per-node N`.
@@ -661,7 +664,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=6)
-    ap.add_argument("--windows", type=int, default=5, help="the K-step window is timed this many times; value = K / median")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="the K-step window is timed this many times; value = K / median (default 1: exactly K timed steps; "
+                         "5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else: single-stream latency, the roofline / kernel-class "
+                         "profiled passes, the cfg 3 / cfg 5 / N=16384 / predict / FITC extras, the collective extras and the "
+                         "CPU baselines.  --prof-steps, --no-cpu-baseline, --cpu-budget, --no-extras, --collective-extras-only, "
+                         "--cfg4-n and --sharded-n act only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as DIR/alpha.npy (N), DIR/nlZ.npy (1) and "
+                         "DIR/dnlZ.npy (mean | cov | lik hypers), float64")
     ap.add_argument("--n", type=int, default=8192)
     ap.add_argument("--d", type=int, default=16)
     ap.add_argument("--prof-steps", type=int, default=6)
@@ -680,6 +693,8 @@ def main():
                     help="size of the one-Cholesky-over-all-ranks extra (SURVEY 8(f)4); -1 = 65536 (34 GB over the ranks); "
                          "0 = skip")
     args = ap.parse_args()
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
 
     # `python3 bench.py --gpus N` with N > 1 and no launcher around it: become the launcher (one rank per GPU under
     # torch.distributed.run, rendezvous on 127.0.0.1) and hand its output through -- rank 0 of the children prints the line
@@ -842,6 +857,11 @@ def main():
             wt = float(tt.item())
         windows.append(wt)
     dt = float(np.median(windows))
+    if rank == 0 and args.dump_outputs:
+        # what the caller of the last timed step received: its fit stream's buffers, before a later fit reuses them
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in zip(("alpha", "nlZ", "dnlZ"), bufs[(args.steps - 1) % S]):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     # every rank's own rate (its median window, before the max over ranks): the 1/2/4/8 table shows stragglers directly
     own = float(np.median(own_windows))
     rank_rates = [args.steps / own]
@@ -850,36 +870,36 @@ def main():
         parts_r = [torch.empty_like(rr) for _ in range(world)]
         dist.all_gather(parts_r, rr)
         rank_rates = [float(p_.item()) for p_ in parts_r]
-    # single-stream latency of one fit in a dependent chain (what cfg 4's one-restart-per-GPU minimize.run sees): the lone-chain schedule
-    if sched_multi:
-        lib.pgp_set_option(ctxs[0], b"sched", -1)          # the library's default for a lone chain (sched 2 since round 5)
-    t1 = time.perf_counter()
-    lat_stage = []
-    for s in range(6):
-        fit(args.warmup + s)
-        lat_stage.append(_lib.last_timings(local))
-    lat_ms = (time.perf_counter() - t1) / 6 * 1e3
-    single_rates = [1e3 / lat_ms]                     # every rank's ONE-chain rate: cfg 4 as written (8 restarts on 8 GPUs) runs one chain per GPU
-    if dist:
-        sr = torch.tensor([1e3 / lat_ms], dtype=torch.float64, device=cdev)
-        parts_s = [torch.empty_like(sr) for _ in range(world)]
-        dist.all_gather(parts_s, sr)
-        single_rates = [float(p_.item()) for p_ in parts_s]
-    # the same with E E^T kept OUT of the sweep (option eet_overlap=0): the stage time of the sweep + fused inverse alone,
-    # the figure rounds 1-2 quote as cholesky_sweep_* (2 N^3 / 3 flops); the default schedule folds E E^T into the sweep
-    sweep_stage = []
-    if lib.pgp_set_option(ctxs[0], b"eet_overlap", 0) == 0:
+    if args.full:
+        # single-stream latency of one fit in a dependent chain (what cfg 4's one-restart-per-GPU minimize.run sees): the lone-chain schedule
+        if sched_multi:
+            lib.pgp_set_option(ctxs[0], b"sched", -1)          # the library's default for a lone chain (sched 2 since round 5)
+        t1 = time.perf_counter()
+        lat_stage = []
         for s in range(6):
             fit(args.warmup + s)
-            sweep_stage.append(_lib.last_timings(local))
-        lib.pgp_set_option(ctxs[0], b"eet_overlap", eet_default)
+            lat_stage.append(_lib.last_timings(local))
+        lat_ms = (time.perf_counter() - t1) / 6 * 1e3
+        single_rates = [1e3 / lat_ms]                     # every rank's ONE-chain rate: cfg 4 as written (8 restarts on 8 GPUs) runs one chain per GPU
+        if dist:
+            sr = torch.tensor([1e3 / lat_ms], dtype=torch.float64, device=cdev)
+            parts_s = [torch.empty_like(sr) for _ in range(world)]
+            dist.all_gather(parts_s, sr)
+            single_rates = [float(p_.item()) for p_ in parts_s]
+        # the same with E E^T kept OUT of the sweep (option eet_overlap=0): the stage time of the sweep + fused inverse alone,
+        # the figure rounds 1-2 quote as cholesky_sweep_* (2 N^3 / 3 flops); the default schedule folds E E^T into the sweep
+        sweep_stage = []
+        if lib.pgp_set_option(ctxs[0], b"eet_overlap", 0) == 0:
+            for s in range(6):
+                fit(args.warmup + s)
+                sweep_stage.append(_lib.last_timings(local))
+            lib.pgp_set_option(ctxs[0], b"eet_overlap", eet_default)
     if dist:
         res = torch.tensor(vals, dtype=torch.float64, device=cdev)
         parts = [torch.empty_like(res) for _ in range(world)]
         dist.all_gather(parts, res)                                              # RCCL gather of results
         vals_all = torch.stack(parts).cpu().numpy()
         assert np.all(np.isfinite(vals_all)) and vals_all.shape == (world, args.steps)
-    stages = {k: float(np.median([t[k] for t in lat_stage])) for k in lat_stage[0]}
 
     # the extra fit-stream contexts of the timed region are done: give their HIP streams back before the extras create
     # their own (beyond four streams of one priority the runtime maps streams onto SHARED hardware queues, and two fit
@@ -892,7 +912,7 @@ def main():
     roof = None
     classes = {}
     extra = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         lib.pgp_profile_reset(ctx)
         lib.pgp_set_profiling(ctx, 1)
         prof_stage = []
@@ -1036,13 +1056,14 @@ def main():
                                       % (S, "" if dist else " (no process group at world size 1)")},
             "per_rank_fits_per_s": rank_rates, "per_gpu_fits_per_s": (total_fits / dt) / world,
             "timed_windows_s": windows, "window_spread": (max(windows) - min(windows)) / dt,
-            "single_stream_ms_per_fit": lat_ms, "single_stream_fits_per_s": 1e3 / lat_ms,
-            "stage_ms_single_stream_median": stages,
             "flops_per_fit": float(N) ** 3,
             "fit_TFLOPs": float(N) ** 3 / (dt / args.steps) / 1e12,
-            "roofline": roof, "kernel_classes": classes,
             "device": _lib.device_info(local),
         }
+        if args.full:
+            out.update({"single_stream_ms_per_fit": lat_ms, "single_stream_fits_per_s": 1e3 / lat_ms,
+                        "stage_ms_single_stream_median": {k: float(np.median([t[k] for t in lat_stage])) for k in lat_stage[0]},
+                        "roofline": roof, "kernel_classes": classes})
         if rccl_note:
             out["rccl_note"] = rccl_note
         out.update({k: v for k, v in extra.items() if k != "api"})
@@ -1054,7 +1075,7 @@ def main():
     #      the contract if the collective path stalls on a node this code has never run on: the JSON line goes out without
     #      the figures and the process leaves.
     sn = args.sharded_n if args.sharded_n >= 0 else 65536     # the same size at every world size: a strong-scaling series
-    if dist and not args.no_extras:
+    if args.full and dist and not args.no_extras:
         dist.barrier()                                       # rank 0 arrives after its single-GPU extras; the clock starts here
         partial = {}
 
@@ -1086,7 +1107,7 @@ def main():
             out.update(partial)
             out["collective_extras_ok"] = all("error" not in v for v in partial.values())
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(N, d, args.cpu_budget)
             out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
             if not args.no_extras:

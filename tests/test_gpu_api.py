@@ -277,14 +277,14 @@ def test_sharded_minimize_over_rccl_world_size_1(lib):
 
 
 def test_bench_line_contract_small(lib):
-    """bench.py end to end at a small size: one JSON line with the contract's keys, the RCCL process group of world
+    """bench.py --full end to end at a small size: one JSON line with the contract's keys, the RCCL process group of world
     size 1 included (the full-size run is the driver's)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--n", "1024", "--steps", "4", "--warmup", "2",
-                          "--windows", "2", "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, timeout=600)
+                          "--windows", "2", "--full", "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = out.stdout.splitlines()
     assert len(lines) == 1, lines        # ONE line on stdout: RCCL's banner and anything else native goes to stderr
@@ -319,6 +319,34 @@ def test_bench_line_contract_small(lib):
     assert not any(k.endswith("_what") or k.endswith("_sched0") or k in ("how", "traffic_source") for k in r)
     assert "how" in j["roofline_detail"] and len(j["roofline_detail"]["kernel"]) > 120
     assert isinstance(j["roofline_detail"]["timed_window"], dict) and r["timed_window_frac_of_peak"] > 0
+
+
+def test_bench_plain_run_headline_and_dumped_outputs(tmp_path):
+    """bench.py without --full: the headline alone (one window of exactly --steps fits, nothing of --full's), and
+    --dump-outputs writes what the last timed fit returned -- checked against the oracle at that step's hyper-parameters."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, d, steps, warmup = 1024, 16, 3, 2
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--n", str(n), "--steps", str(steps), "--warmup",
+                          str(warmup), "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = out.stdout.splitlines()
+    assert len(lines) == 1, lines
+    j = json.loads(lines[0])
+    assert j["steps"] == steps and j["unit"] == "fits/s" and j["higher_is_better"] is True and j["dtype"] == "f64"
+    assert len(j["timed_windows_s"]) == 1 and abs(j["ms_per_step"] * steps - j["timed_windows_s"][0] * 1e3) < 1e-9 * j["ms_per_step"]
+    assert abs(j["value"] * j["ms_per_step"] - 1e3) < 1e-9 * 1e3
+    for k in ("roofline", "kernel_classes", "single_stream_ms_per_fit", "cpu_baseline", "cfg3_seard_N16384_d64", "api"):
+        assert k not in j, k
+    alpha, nlZ, dnlZ = (np.load(os.path.join(tmp_path, f + ".npy")) for f in ("alpha", "nlZ", "dnlZ"))
+    assert alpha.dtype == nlZ.dtype == dnlZ.dtype == np.float64 and alpha.shape == (n,) and nlZ.shape == (1,) and dnlZ.shape == (4,)
+    sys.path.insert(0, root)
+    import bench
+    x, y = bench.synth_reg(n, d)
+    hyp, log_sn = bench.hyp_for(warmup + steps - 1, 0, d)
+    ref = O.exact_fit(O.RBF, hyp, 0, log_sn, x, y, y.mean() * np.ones_like(y), np.ones_like(y), nargout=3, faithful=False)
+    want = np.concatenate([ref["dnlZ_mean"], ref["dnlZ_cov"], ref["dnlZ_lik"]])
+    assert abs(nlZ[0] - ref["nlZ"]) <= 1e-9 * abs(ref["nlZ"])
+    assert relerr(alpha, np.ravel(ref["alpha"])) <= 1e-7 and relerr(dnlZ, want) <= 1e-7
 
 
 def test_exact_rejects_non_gaussian_and_unknown_kernel(lib):
@@ -546,7 +574,7 @@ def test_bench_collective_extras_ranks_sharing_one_gpu(tmp_path, world, stub):
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
                           "--gpus", str(world), "--steps", "4", "--warmup", "2", "--windows", "1",   # (no --n: torchrun's parser trips on it)
-                          "--no-cpu-baseline", "--collective-extras-only", "--cfg4-n", "512", "--sharded-n", "4096"],
+                          "--full", "--no-cpu-baseline", "--collective-extras-only", "--cfg4-n", "512", "--sharded-n", "4096"],
                          capture_output=True, text=True, timeout=1200, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -569,7 +597,7 @@ def test_bench_launches_itself_on_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["PYGPS_BENCH_BACKEND"] = "gloo"
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                          "--windows", "1", "--no-cpu-baseline", "--collective-extras-only", "--cfg4-n", "512",
+                          "--windows", "1", "--full", "--no-cpu-baseline", "--collective-extras-only", "--cfg4-n", "512",
                           "--sharded-n", "2048"], capture_output=True, text=True, timeout=1200, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]

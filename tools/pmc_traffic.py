@@ -51,7 +51,7 @@ if __name__ == "__main__":
                "fetch_bytes_per_launch": fetch_b, "write_bytes_per_launch": write_b,
                "bytes_per_launch": fetch_b + write_b,
                "all_gemm_f64_instantiations": {"launches_sampled": nfa, "bytes_per_launch": fa * 2048.0 / nfa + wa * 1024.0 / nwa},
-               "note": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over `python bench.py --steps 3 --windows 1 --prof-steps 1 --streams 1 "
+               "note": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over `python bench.py --full --steps 3 --windows 1 --prof-steps 1 --streams 1 "
                        "--warmup 1 --no-cpu-baseline --no-extras`, dispatches of that instantiation averaged; FETCH_SIZE x2 "
                        "(gfx950 wide-load correction, MI355X_MICROARCH.md HBM section), KiB -> bytes"},
               open(out, "w"), indent=1)
