@@ -133,6 +133,30 @@ int pgp_ep_fit_dense(pgp_ctx* ctx, const double* K, const double* mvec, const do
                      double* ttau_io, double* tnu_io, double* alpha_out, double* sW_out, double* nlZ_out,
                      double* dnlZ_mean_out, int* sweeps_out, pgp_factor** factor_out);
 
+/* ---- Laplace.evaluate with lik.Erf or lik.Gauss (Core/inf.py:459-564; Core/lik.py:175-197, 274-293) -----------------------
+ * The Newton iteration in f with Brent's line search (inf.py:466-512, tools.py:121-272: tol 1e-6, at most 20 steps, s in [0, 2],
+ * at most 20 evaluations per line search, thr 1e-4), then the posterior (inf.py:514-529) and, for want = 3, the gradients with
+ * their implicit part (inf.py:530-562).  lik: PGP_LIK_ERF (likhyp unused, nlik = 0) or PGP_LIK_GAUSS (likhyp = [log sn], nlik = 1).
+ * alpha_io (n): in = the last alpha (Laplace.last_alpha; used only if warm != 0, and kept only if its objective beats the default
+ * start f = m as inf.py:474-497 decides), out = the final alpha.  sW_out (n), nlZ_out (1), dnlZ_out (nmean + ncov + nlik, order
+ * mean | cov | lik).  steps_out: Newton steps taken.  trace_out (optional, 3 x 20): per Newton step the line search's step size,
+ * objective Psi and number of evaluations.  factor_out: the posterior handle, the same form as EP's (pgp_predict serves it).
+ * PGP_ERR_LAPLACE_WNEG: some W_i = -d2lp_i < 0 (the reference's LU branch, inf.py:500-502 / 520-523, is not restated; it cannot
+ * occur for Erf or Gauss).  Other status codes as pgp_ep_fit. */
+#define PGP_LIK_ERF 0
+#define PGP_LIK_GAUSS 1
+#define PGP_ERR_LAPLACE_WNEG (-90)
+int pgp_laplace_fit(pgp_ctx* ctx, int kind, const double* covhyp, int ncov, int para, int flags, int lik, const double* likhyp,
+                    int nlik, const double* mvec, const double* dm, int nmean, int want, int warm, double* alpha_io,
+                    double* sW_out, double* nlZ_out, double* dnlZ_out, int* steps_out, double* trace_out, pgp_factor** factor_out);
+/* Laplace.evaluate from a CALLER-BUILT covariance matrix K (n, n) (the covariance trees of Core/cov.py:230-328 that are not device
+ * programs); n, y as set by pgp_set_data.  dnlZ_out: nmean + nlik entries (mean, then lik).  want = 3 leaves
+ * R = sW sW' o B^-1 - u dlp' - dlp u' and alpha in the context's workspace: pgp_dense_grad_term(ctx, dK_h, n, 0.0, &g) directly
+ * afterwards gives dnlZ.cov[h] (inf.py:536-541).  Other arguments and status codes as pgp_laplace_fit. */
+int pgp_laplace_fit_dense(pgp_ctx* ctx, const double* K, int lik, const double* likhyp, int nlik, const double* mvec,
+                          const double* dm, int nmean, int want, int warm, double* alpha_io, double* sW_out, double* nlZ_out,
+                          double* dnlZ_out, int* steps_out, double* trace_out, pgp_factor** factor_out);
+
 /* ---- FITC sparse regression: FITC_Exact.evaluate (Core/inf.py:398-455) with FITCOfKernel (Core/cov.py:332-390)
  * x, y of the last pgp_set_data; xu (nu,d) inducing inputs.  alpha_out (nu), L_out (nu,nu) = post.L (dense,
  * symmetric; NULL to skip), dnlZ_out = [mean.., cov.., lik].  snu2 = 1e-6 sn2 like the reference (inf.py:410).

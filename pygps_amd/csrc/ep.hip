@@ -946,6 +946,13 @@ struct EpWork {
 
 }  // namespace
 
+// ep_build_kernel for the other drivers (laplace.hip): F = I + s s' o K (lower), Y = diag(s) K or, with colscale, K diag(s)
+int ep_build_launch(const double* K, long np, const double* s, double* F, long ldf, double* Y, int colscale, hipStream_t st) {
+    hipLaunchKernelGGL(ep_build_kernel, dim3((unsigned)((np + 255) / 256), (unsigned)std::min<long>(np, 65535)), dim3(256), 0, st, K, np,
+                       s, F, ldf, Y, colscale);
+    return hipGetLastError() == hipSuccess ? PGP_OK : PGP_ERR_HIP;
+}
+
 // recompute Sigma, mu, L from (ttau, tnu) and return nlZ (inf.py:174-189).  Host vectors in/out.
 static int ep_compute_params(pgp_ctx* c, EpWork& w, const std::vector<double>& y, const std::vector<double>& m,
                              const std::vector<double>& ttau, const std::vector<double>& tnu, double* nlZ_out,

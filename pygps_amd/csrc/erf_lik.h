@@ -43,3 +43,26 @@ PGP_HD inline void erf_ep_moments(double y, double mu, double s2, double* lZ, do
         if (d2lZ) *d2lZ = -n_p * (z + n_p) / (1.0 + s2);
     }
 }
+
+// Laplace mode (Core/lik.py:274-293): lp, dlp, d2lp, d3lp of log Phi(y f) in f, y in {+1,-1} (0 counts as +1).  The ratio
+// N(yf) / Phi(yf) takes Phi itself, not exp(log Phi) as the EP mode does (lik.py:278-280); the asymptotic / blended branches
+// of erf_logphi and erf_ratio are shared with the EP mode.
+PGP_HD inline void erf_laplace_derivs(double y, double f, double* lp, double* dlp, double* d2lp, double* d3lp) {
+    const double ys = (y < 0.0) ? -1.0 : 1.0;
+    const double yf = ys * f;
+    *lp = erf_logphi(yf);
+    const double p = 0.5 * (1.0 + erf(yf * 0.70710678118654752440));
+    const double n_p = erf_ratio(yf, p);
+    *dlp = ys * n_p;
+    *d2lp = -n_p * n_p - yf * n_p;
+    if (d3lp) *d3lp = 2.0 * ys * n_p * n_p * n_p + 3.0 * f * n_p * n_p + ys * (f * f - 1.0) * n_p;
+}
+
+// Gauss, Laplace mode (Core/lik.py:175-189): sn2 = exp(2 log_sn)
+PGP_HD inline void gauss_laplace_derivs(double y, double f, double sn2, double* lp, double* dlp, double* d2lp, double* d3lp) {
+    const double r = y - f;
+    *lp = -r * r / (2.0 * sn2) - 0.5 * log(2.0 * M_PI * sn2);
+    *dlp = r / sn2;
+    *d2lp = -1.0 / sn2;
+    if (d3lp) *d3lp = 0.0;
+}

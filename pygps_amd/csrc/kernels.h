@@ -70,6 +70,9 @@ int col_sumsq_launch(const double* A, long lda, long nrows, long ncols, double k
                      hipStream_t st);
 int row_scale_launch(double* A, long lda, long nrows, long ncols, const double* s, hipStream_t st);
 
+// ep.hip: F (column-major lower, ldf) = I + s s' o K; Y = diag(s) K, or K diag(s) with colscale (Y may be null)
+int ep_build_launch(const double* K, long np, const double* s, double* F, long ldf, double* Y, int colscale, hipStream_t st);
+
 // grad.hip (fused-inverse helpers)
 int identity_upper_launch(double* E, long lde, long np, hipStream_t st);
 int upper_matvec_launch(const double* E, long lde, long np, const double* z, double scale, double* partial, double* y,

@@ -18,6 +18,9 @@ int pgp_test_gemm_shrink(pgp_ctx* ctx, const double* Y, int64_t ldy, int M, int 
 int pgp_test_gemm_skip_wait(pgp_ctx* ctx, int tile, const double* A, const double* B, double* C, int n, int K, int skip_lo,
                             int skip_hi, int wait_ms, int* timed_out);
 int pgp_test_probit_hazard(pgp_ctx* ctx, const double* z, double* out, int n);
+/* the Laplace-mode likelihood derivatives of the device (csrc/erf_lik.h) at host (y, f): out (4, n) rows lp, dlp, d2lp, d3lp.
+   lik: PGP_LIK_ERF or PGP_LIK_GAUSS (log_sn used for Gauss only) */
+int pgp_test_laplace_lik(pgp_ctx* ctx, int lik, double log_sn, const double* y, const double* f, int n, double* out);
 int pgp_test_valu_peak(pgp_ctx* ctx, int iters, int waves_per_simd, double* out2);
 int pgp_test_mfma_peak(pgp_ctx* ctx, int iters, double* tflops_out);
 int pgp_test_mfma_cycles(pgp_ctx* ctx, int iters, int nacc, int waves_per_simd, double* out3);

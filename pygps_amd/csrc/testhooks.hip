@@ -10,6 +10,7 @@
 #include <thread>
 
 #include "testhooks.h"
+#include "erf_lik.h"
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
@@ -709,5 +710,33 @@ extern "C" int pgp_test_stream_concurrency(pgp_ctx* c, int wait_us, double* out2
     long long h[2] = {0, 0};
     HIP_TRY(hipMemcpy(h, res, sizeof(h), hipMemcpyDeviceToHost));
     out2[0] = (double)h[0]; out2[1] = (double)h[1] / 100.0;
+    return PGP_OK;
+}
+
+namespace {
+__global__ void laplace_lik_test_kernel(int lik, double sn2, const double* __restrict__ y, const double* __restrict__ f,
+                                        double* __restrict__ out, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double lp, d1, d2, d3;
+    if (lik == PGP_LIK_GAUSS) gauss_laplace_derivs(y[i], f[i], sn2, &lp, &d1, &d2, &d3);
+    else erf_laplace_derivs(y[i], f[i], &lp, &d1, &d2, &d3);
+    out[i] = lp; out[n + i] = d1; out[2L * n + i] = d2; out[3L * n + i] = d3;
+}
+}  // namespace
+
+// self-test hook: the Laplace-mode likelihood derivatives (csrc/erf_lik.h) on the device, rows lp, dlp, d2lp, d3lp of out (4, n)
+extern "C" int pgp_test_laplace_lik(pgp_ctx* c, int lik, double log_sn, const double* y, const double* f, int n, double* out) {
+    if (!c || !y || !f || !out || n <= 0) return -1;
+    if (lik != PGP_LIK_ERF && lik != PGP_LIK_GAUSS) return -2;
+    HIP_TRY(hipSetDevice(c->device));
+    DevScratch scr;
+    double *yd, *fd, *od;
+    CHK(scr.alloc(&yd, (size_t)n * 8)); CHK(scr.alloc(&fd, (size_t)n * 8)); CHK(scr.alloc(&od, (size_t)4 * n * 8));
+    HIP_TRY(hipMemcpy(yd, y, (size_t)n * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(fd, f, (size_t)n * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(laplace_lik_test_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->st, lik, exp(2.0 * log_sn), yd, fd, od, n);
+    HIP_TRY(hipStreamSynchronize(c->st));
+    HIP_TRY(hipMemcpy(out, od, (size_t)4 * n * 8, hipMemcpyDeviceToHost));
     return PGP_OK;
 }

@@ -199,10 +199,13 @@ class GPR(GP):
         self.likfunc = lik.Gauss(log_sigma)
 
     def useInference(self, newInf):
-        if newInf == "EP":
+        """'Laplace' or 'EP' (Core/gp.py:611-622)."""
+        if newInf == "Laplace":
+            self.inffunc = inf.Laplace()
+        elif newInf == "EP":
             self.inffunc = inf.EP()
         else:
-            raise Exception('Possible inf values are "EP" (Laplace is out of scope of pygps_amd).')
+            raise Exception('Possible inf values are "Laplace", "EP".')
 
 
 class GPC(GP):
@@ -217,10 +220,13 @@ class GPC(GP):
         self.optimizer = opt.Minimize(self)
 
     def useInference(self, newInf):
-        if newInf == "EP":
+        """'Laplace' or 'EP' (Core/gp.py:708-717; the reference's GPC also accepts only these)."""
+        if newInf == "Laplace":
+            self.inffunc = inf.Laplace()
+        elif newInf == "EP":
             self.inffunc = inf.EP()
         else:
-            raise Exception('Possible inf values are "EP" (Laplace is out of scope of pygps_amd).')
+            raise Exception('Possible inf values are "Laplace", "EP".')
 
 
 class GP_FITC(GP):

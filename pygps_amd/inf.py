@@ -1,5 +1,5 @@
 """Inference engines on the hot path (reference: pyGPs/Core/inf.py -- postStruct :59-89,
-dnlZStruct :93-128, Inference :133-172, Exact :345-384, EP :723-806).
+dnlZStruct :93-128, Inference :133-172, Exact :345-384, Laplace :459-564, EP :723-806).
 
 ``Exact.evaluate`` keeps the reference's signature and result types but the whole body -- kernel
 assembly, Cholesky, solves, nlZ and all hyper-gradients -- is ONE call into the device pipeline
@@ -467,6 +467,99 @@ class EP(Inference):
                 dnlZ.cov.append(np.float64(gh[0]))
             dnlZ.mean = [np.float64(v) for v in g[:nm]]
             dnlZ.lik = []
+            return post, np.float64(nlZ[0]), dnlZ
+        return post, np.float64(nlZ[0])
+
+
+class Laplace(Inference):
+    """Laplace's approximation to the posterior (Core/inf.py:459-564) with lik.Erf or lik.Gauss: the Newton iteration in f
+    with Brent's line search, the posterior and the gradients with their implicit part, all in ONE device call
+    (csrc/laplace.hip).  ``last_alpha`` persists across calls and warm-starts the next one as the reference's does
+    (inf.py:474-497); one of another length starts cold.  ``newton_steps``: Newton steps of the last call;
+    ``last_steps``: (step size, objective, evaluations) of each of its line searches."""
+
+    def __init__(self):
+        self.name = "Laplace's Approximation"
+        self.last_alpha = None
+        self.device = None
+        self.newton_steps = 0
+        self.last_steps = np.zeros((0, 3))
+        self._tol_exp = None            # private: Newton tolerance 10^-_tol_exp instead of the reference's 1e-6 (gradient checks)
+
+    def _lik_args(self, likfunc):
+        if isinstance(likfunc, _lik.Erf):
+            return _lib.LIK_ERF, None, 0
+        if isinstance(likfunc, _lik.Gauss):
+            return _lib.LIK_GAUSS, _lib.f64(np.asarray(likfunc.hyp, dtype=float)), 1
+        raise NotImplementedError("pygps_amd: Laplace runs on the device for lik.Erf and lik.Gauss only (no CPU fallback)")
+
+    def evaluate(self, meanfunc, covfunc, likfunc, x, y, nargout=1):
+        lik, likhyp, nlik = self._lik_args(likfunc)
+        dev = _lib.default_device() if self.device is None else self.device
+        dense = isinstance(covfunc, _cov._Composite) and not covfunc._on_device()
+        if not dense:
+            kind, para, flags = _device_kernel(covfunc, _lib.ctx(dev))
+        x = _lib.f64(x)
+        n, D = x.shape
+        y = _lib.f64(y).reshape(n)
+        DeviceFactor.reserve(n, dev)
+        _Resident.ensure(x, y, dev)
+        m, dm, nm = _mean_inputs(meanfunc, x)
+        hyp = _lib.f64(np.asarray(covfunc.hyp, dtype=float))
+        nc = 0 if dense else len(hyp)
+        last = None if self.last_alpha is None else np.asarray(self.last_alpha, dtype=float).reshape(-1)
+        warm = last is not None and last.shape[0] == n
+        alpha = _lib.f64(last).copy() if warm else np.zeros(n)
+        sW = np.empty(n)
+        nlZ = np.zeros(1)
+        g = np.zeros(nm + nc + nlik + 1)
+        steps = C.c_int()
+        trace = np.zeros((20, 3))
+        fh = C.c_void_p()
+        want = int(min(max(nargout, 1), 3))
+        lib = _lib.load()
+        ctx = _lib.ctx(dev)
+        if self._tol_exp is not None:
+            _lib.check(lib.pgp_set_option(ctx, b"laplace_tol_exp", int(self._tol_exp)), "pgp_set_option")
+        try:
+            if dense:
+                K = _lib.f64(covfunc.getCovMatrix(x=x, mode="train"))
+                rc = lib.pgp_laplace_fit_dense(ctx, _lib.ptr(K), lik, _lib.ptr(likhyp), nlik, _lib.ptr(m), _lib.ptr(dm), nm, want,
+                                               int(warm), _lib.ptr(alpha), _lib.ptr(sW), _lib.ptr(nlZ), _lib.ptr(g),
+                                               C.byref(steps), _lib.ptr(trace), C.byref(fh))
+                del K
+            else:
+                rc = lib.pgp_laplace_fit(ctx, kind, _lib.ptr(hyp), nc, int(para), int(flags), lik, _lib.ptr(likhyp), nlik,
+                                         _lib.ptr(m), _lib.ptr(dm), nm, want, int(warm), _lib.ptr(alpha), _lib.ptr(sW),
+                                         _lib.ptr(nlZ), _lib.ptr(g), C.byref(steps), _lib.ptr(trace), C.byref(fh))
+        finally:
+            if self._tol_exp is not None:
+                lib.pgp_set_option(ctx, b"laplace_tol_exp", 6)
+        if rc == _lib.ERR_LAPLACE_WNEG:
+            raise NotImplementedError("pygps_amd: Laplace met W < 0 (the reference's LU branch is not restated)")
+        _lib.check(rc, "pgp_laplace_fit_dense" if dense else "pgp_laplace_fit")
+        self.newton_steps = steps.value
+        self.last_steps = trace[:self.newton_steps].copy()
+        self.last_alpha = alpha.reshape(n, 1)                   # inf.py:513
+        post = postStruct()
+        post.alpha = alpha.reshape(n, 1).copy()
+        post.sW = sW.reshape(n, 1)
+        post.L = DeviceFactor(fh, n, dev, _lib.current_slot())
+        if dense:
+            post.L.dense = True                                 # predict hands the cross-covariance block in (GP._latent)
+        if nargout > 2:
+            dnlZ = dnlZStruct(meanfunc, covfunc, likfunc)
+            dnlZ.mean = [np.float64(v) for v in g[:nm]]
+            if dense:
+                gh = np.zeros(1)
+                dnlZ.cov = []
+                for h in range(len(hyp)):                       # one derivative matrix at a time (inf.py:536-541)
+                    dK = _lib.f64(covfunc.getDerMatrix(x=x, mode="train", der=h))
+                    _lib.check(lib.pgp_dense_grad_term(ctx, _lib.ptr(dK), n, 0.0, _lib.ptr(gh)), "pgp_dense_grad_term")
+                    dnlZ.cov.append(np.float64(gh[0]))
+            else:
+                dnlZ.cov = [np.float64(v) for v in g[nm:nm + nc]]
+            dnlZ.lik = [np.float64(v) for v in g[nm + nc:nm + nc + nlik]]
             return post, np.float64(nlZ[0]), dnlZ
         return post, np.float64(nlZ[0])
 

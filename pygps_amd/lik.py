@@ -2,7 +2,8 @@
 
 ``Gauss`` is the type gate and noise source of Exact inference (Core/inf.py:354,360) and supplies
 the predictive moments (Core/gp.py:422-427); ``Erf`` supplies the probit predictive and the EP site
-moments.  All of it is O(N) scalar host work."""
+moments.  Both have the Laplace mode (lp and its derivatives in f, Core/lik.py:175-197, 274-293); the
+Laplace fit itself evaluates them on the device (csrc/erf_lik.h).  All of it is O(N) scalar host work."""
 import numpy as np
 from scipy.special import erf as _erf
 
@@ -42,6 +43,14 @@ class Gauss(Likelihood):
                 v = sn2 + s2
                 return _take((-(y - mu) ** 2 / v / 2. - np.log(2 * np.pi * v) / 2., (y - mu) / v, -1 / v), nargout)
             return ((y - mu) ** 2 / (sn2 + s2) - 1) / (1 + s2 / sn2)
+        if isinstance(inffunc, inf.Laplace):                  # lik.py:175-197
+            if y is None:
+                y = 0
+            if der is None:
+                r = y - mu
+                lp = -r ** 2 / (2 * sn2) - np.log(2 * np.pi * sn2) / 2.
+                return _take((lp, r / sn2, -np.ones_like(r) / sn2, np.zeros_like(r)), nargout)
+            return (y - mu) ** 2 / sn2 - 1, 2 * (mu - y) / sn2, 2 * np.ones_like(mu) / sn2
         raise Exception("Incorrect inference in lik.Gauss\n")
 
 
@@ -103,6 +112,19 @@ class Erf(Likelihood):
             else:
                 p, lp = self.cumGauss(y, mu, 2)
             return _take((lp, 2 * p - 1, 4 * p * (1 - p)), nargout)
+        if isinstance(inffunc, inf.Laplace):                  # lik.py:274-293
+            if der is not None:
+                return []
+            f = mu
+            yf = y * f
+            p, lp = self.cumGauss(y, f, 2)
+            if nargout <= 1:
+                return lp
+            n_p = self._ratio(yf, p)                          # N / Phi from Phi itself (the EP mode passes exp(log Phi))
+            dlp = y * n_p
+            d2lp = -n_p ** 2 - yf * n_p
+            d3lp = 2 * y * n_p ** 3 + 3 * f * n_p ** 2 + y * (f ** 2 - 1) * n_p
+            return _take((lp, dlp, d2lp, d3lp), nargout)
         if isinstance(inffunc, inf.EP):                       # lik.py:295-313
             if der is not None:
                 return []

@@ -184,12 +184,12 @@ class ShardedMinimize(Minimize):
     @staticmethod
     def _cold_start(model):
         """A restart must not depend on which restart ran before it on the same model object: inference methods that
-        keep warm-start state between evaluations (EP: last_ttau / last_tnu, Core/inf.py:735-741) begin every restart
+        keep warm-start state between evaluations (EP: last_ttau / last_tnu, Core/inf.py:735-741; Laplace: last_alpha) begin every restart
         cold.  The sequential reference carries that state from one restart into the next; a sharded search cannot
         (the predecessor runs on another GPU), so it defines the per-restart result as the cold-started one -- the same
         on every world size, fit-stream count and timing."""
         inf = getattr(model, "inffunc", None)
-        for name in ("last_ttau", "last_tnu"):
+        for name in ("last_ttau", "last_tnu", "last_alpha"):          # EP, Laplace (Core/inf.py:474)
             if hasattr(inf, name):
                 setattr(inf, name, None)
 

@@ -87,7 +87,7 @@ def _one_fold(make_model, x, y, K, k, metrics, numIterations, set_data):
     m = make_model()
     x_tr, y_tr, x_te, y_te = x[~test], y[~test], x[test], y[test]
     inf_ = getattr(m, "inffunc", None)
-    for name in ("last_ttau", "last_tnu"):           # a fold never inherits EP warm-start state (cf. ShardedMinimize._cold_start)
+    for name in ("last_ttau", "last_tnu", "last_alpha"):   # a fold never inherits EP / Laplace warm-start state (cf. ShardedMinimize._cold_start)
         if hasattr(inf_, name):
             setattr(inf_, name, None)
     if set_data:                                      # the documented flow: setData (the default mean becomes Const(mean(y_train)),
