@@ -217,6 +217,11 @@ __device__ __forceinline__ double matern_dpoly(int d, double t) {
         default: return (t + 3.0 * t * t + t * t * t) / 15.0;
     }
 }
+// f - df/dt itself: differs from the reference's dfunc at d = 7 (Core/cov.py:1114 drops a factor 3 on the linear term), so the
+// correct derivative (no reference_compat) uses this one
+__device__ __forceinline__ double matern_dpoly_exact(int d, double t) {
+    return d == 7 ? (3.0 * t + 3.0 * t * t + t * t * t) / 15.0 : matern_dpoly(d, t);
+}
 
 // PiecePoly polynomial f(v, r, j) and "f - f'" companion (Core/cov.py:698-720)
 __device__ __forceinline__ double pp_func(int v, double r, double j) {
@@ -406,7 +411,7 @@ __device__ __forceinline__ double cov_deriv(const CovParams& p, double s, double
         return p.der == 0 ? p.sf2 * matern_dpoly(p.md, K) * K *  exp_nonpos(-K)
                           : 2.0 * p.sf2 * matern_poly(p.md, K) *  exp_nonpos(-K);
     }
-    return p.der == 0 ? p.sf2 * matern_dpoly(p.md, t) * t *  exp_nonpos(-t)
+    return p.der == 0 ? p.sf2 * matern_dpoly_exact(p.md, t) * t *  exp_nonpos(-t)
                       : 2.0 * p.sf2 * matern_poly(p.md, t) *  exp_nonpos(-t);
 }
 
@@ -471,7 +476,7 @@ __device__ __forceinline__ void cov_deriv_all(const CovParams& p, double s, doub
         d0 = p.sf2 * matern_dpoly(p.md, K) * K * eK;
         d1 = 2.0 * p.sf2 * matern_poly(p.md, K) * eK;
     } else {
-        d0 = p.sf2 * matern_dpoly(p.md, t) * t * e;
+        d0 = p.sf2 * matern_dpoly_exact(p.md, t) * t * e;
         d1 = 2.0 * p.sf2 * matern_poly(p.md, t) * e;
     }
 }
