@@ -169,6 +169,18 @@ int pgp_fitc_predict(pgp_ctx* ctx, pgp_fitc* f, const double* xs, int64_t ns, co
                      double* fs2);
 void pgp_fitc_free(pgp_ctx* ctx, pgp_fitc* f);
 
+/* ---- FITC sparse classification: FITC_EP.evaluate (Core/inf.py:810-944) with lik.Erf and FITCOfKernel --------------------
+ * EP on Kt = Q + diag(K - Q) in O(n nu) memory, snu2 = 1e-6 (Erf has no hyper-parameter, inf.py:837-841): tol 1e-4, 2 to 10
+ * sweeps over the sites in order 0..n-1, 128-site blocks (csrc/fitc.hip), a refresh and _epfitcZ's nlZ after every sweep.
+ * warm != 0: ttau_io / tnu_io (n) hold the previous call's site parameters and are tried against nlZ0 as inf.py:857-870 does;
+ * on return they hold the final ones.  alpha_out (nu), L_out (nu x nu row-major), nlZ_out, dnlZ_out (nmean + ncov: mean,
+ * then covariance gradients), sweeps_out.  Returns >0 when a Cholesky pivot is not positive.  handle_out (optional) feeds
+ * pgp_fitc_predict. */
+int pgp_fitc_ep_fit(pgp_ctx* ctx, int kind, const double* covhyp, int ncov, int para, int flags, const double* xu, int64_t nu,
+                    const double* mvec, const double* dm, int nmean, int want, int warm, double* ttau_io, double* tnu_io,
+                    double* alpha_out, double* L_out, double* nlZ_out, double* dnlZ_out, int* sweeps_out,
+                    pgp_fitc** handle_out);
+
 /* ---- ONE fit over the GPUs of a node (no reference counterpart: Core/inf.py:353-384 runs on one host) ---
  * One process per GPU, every rank calls with the same data (pgp_set_data) and arguments.  The factorisation is 1-D
  * block-cyclic over column panels; panels are broadcast over `comm`, alpha / nlZ / dnlZ come back identical on every

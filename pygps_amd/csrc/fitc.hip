@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "erf_lik.h"
 
 struct pgp_fitc {
     long nu = 0, nup = 0;
@@ -447,6 +448,409 @@ void pgp_fitc_free(pgp_ctx* c, pgp_fitc* f) { GateShared device_gate_hold(c);
     spool_give(c, (size_t)f->nup * sizeof(double), f->alpha);
     spool_give(c, (size_t)f->nup * f->nup * sizeof(double), f->Lpost);
     delete f;
+}
+
+}  // extern "C"
+
+// ==== FITC_EP: EP with the probit likelihood on Kt = Q + diag(d0) (reference: FITC_EP.evaluate Core/inf.py:828-944,
+// _epfitcZ :235-255, _epfitcRefresh :257-275, _epfitcUpdate :277-297) ======================================================
+// With V = Luu'^-1 Ku, d0 = diagK - colsum(V o V), site parameters w = ttau, b = tnu, t = 1/(1 + d0 w), s = w t:
+//   A = I + V diag(s) V' = Lu'Lu,  M = A^-1,  h = M V (t o b),  Sigma = diag(d0 t) + diag(t) V'MV diag(t),  mu = Sigma b.
+// (the reference carries the same posterior as d, P, R with R'R = M, nn, gg.)  The site loop is the BLOCK sweep of dense EP:
+// for a block B of 128 consecutive sites
+//   X = M V_B, G = V_B' X  ->  Sigma_BB = diag(d0 t)_B + diag(t_B) G diag(t_B),  mu_B = (d0 t b)_B + t_B o (V_B' h)
+//   fitc_ep_chain_kernel: the 128 dependent site updates of inf.py:879-892 on (Sigma_BB, mu_B), one workgroup
+//   fold, D = diag(s_new - s_old)_B, delta = (t o b)_new - (t o b)_old on B:
+//     M <- M - X Y X',  Y = (I + D G)^-1 D = D - D G_new D  with G_new = V_B' M_new V_B read off Sigma_BB,new
+//     h <- h + X r,     r = delta - Y (V_B' h + G delta)
+// Per sweep that is ~4 n nu^2 flops of skinny GEMMs.  After every sweep the posterior is rebuilt from scratch (inf.py:895)
+// with FITC_Exact's I + Vs Vs' GEMM and fused-inverse Cholesky (Vs = V diag(sqrt s)), and _epfitcZ's nlZ follows from
+// U = E2' V (E2 = Lu^-1): diag(V'MV) = colsum(U o U), V'h = U' be, be = Lu'^-T V (t o b) riding along the factorisation.
+// The posterior and the gradients have the shape of FITC_Exact's with the per-point 1/g replaced by s and the residual
+// (y - m)/g by t o b (inf.py:899-932 read with dd = s, tnu/ttau dd = t o b).
+namespace {
+
+constexpr int FEB = 128;                       // sites per block
+
+// lZ, dlZ, d2lZ -> new site parameters (inf.py:879-890; the same scalar update as dense EP, inf.py:759-767)
+__device__ __forceinline__ void fitc_ep_site(double sii, double mui, double w, double b, double m, double y, double& w_new,
+                                             double& b_new) {
+    const double tau_ni = 1.0 / sii - w;
+    const double nu_ni = mui / sii + m * tau_ni - b;
+    double lZ, dlZ, d2lZ;
+    erf_ep_moments(y, nu_ni / tau_ni, 1.0 / tau_ni, &lZ, &dlZ, &d2lZ);
+    w_new = fmax(-d2lZ / (1.0 + d2lZ / tau_ni), 0.0);
+    b_new = (dlZ + (m - nu_ni / tau_ni) * d2lZ) / (1.0 + d2lZ / tau_ni);
+}
+
+// One workgroup of 256 threads runs the sites i0 .. i0 + nb - 1 in order.  Thread (j = tid % 128, half = tid / 128) keeps
+// Sigma_BB(64 half + q, j), q < 64, in registers; column k of Sigma_BB goes through LDS (double-buffered) to every thread.
+// In:  G = V_B' M V_B (128 x 128), vh = V_B' h, d0, y, m, w, b of the block.  Out: w, b updated in place, Y (128 x 128) and r.
+__global__ __launch_bounds__(256) void fitc_ep_chain_kernel(const double* __restrict__ G, const double* __restrict__ vh,
+                                                            const double* __restrict__ d0g, const double* __restrict__ yg,
+                                                            const double* __restrict__ mg, double* __restrict__ wg,
+                                                            double* __restrict__ bg, int nb, double* __restrict__ Y,
+                                                            double* __restrict__ r) {
+    __shared__ double col[2][FEB], mu[FEB], d0[FEB], tt[FEB], dd[FEB], dl[FEB], vv[FEB], part[2][FEB];
+    __shared__ double pw[FEB], pb[FEB], pm[FEB], py[FEB], cq[2];
+    const int tid = threadIdx.x, j = tid & (FEB - 1), half = tid >> 7, r0 = 64 * half;
+    if (tid < FEB) {
+        const bool live = tid < nb;
+        const double w = live ? wg[tid] : 0.0, b = live ? bg[tid] : 0.0, dz = live ? d0g[tid] : 0.0;
+        const double t = 1.0 / (1.0 + dz * w);
+        pw[tid] = w; pb[tid] = b; pm[tid] = live ? mg[tid] : 0.0; py[tid] = live ? yg[tid] : 1.0;
+        d0[tid] = dz; tt[tid] = t;
+        dd[tid] = w * t;                                           // s_old, becomes s_new - s_old below
+        dl[tid] = t * b;                                           // (t o b)_old
+        mu[tid] = dz * t * b + t * vh[tid];
+    }
+    __syncthreads();
+    double S[64];
+    const double tj = tt[j];
+#pragma unroll
+    for (int q = 0; q < 64; ++q) {
+        const int i = r0 + q;
+        S[q] = tt[i] * G[i + (long)j * FEB] * tj + (i == j ? d0[i] * tt[i] : 0.0);
+    }
+    if (j == 0)
+#pragma unroll
+        for (int q = 0; q < 64; ++q) col[0][r0 + q] = S[q];
+    __syncthreads();
+    for (int k = 0; k < nb; ++k) {
+        const int bf = k & 1;
+        if (tid == 0) {
+            const double sii = col[bf][k], mui = mu[k], w = pw[k], b = pb[k];
+            double w_new, b_new;
+            fitc_ep_site(sii, mui, w, b, pm[k], py[k], w_new, b_new);
+            const double ds2 = w_new - w, dn = b_new - b;
+            const double c = ds2 / (1.0 + ds2 * sii);                        // Sigma -= c s s'  (inf.py:769)
+            cq[0] = c;
+            cq[1] = dn * (1.0 - c * sii) - c * mui;                          // mu += q s  (mu = Sigma tnu)
+            pw[k] = w_new; pb[k] = b_new;
+        }
+        __syncthreads();
+        const double c = cq[0], qm = cq[1], sj = col[bf][j];
+#pragma unroll
+        for (int q = 0; q < 64; ++q) S[q] = fma(-c * col[bf][r0 + q], sj, S[q]);
+        if (tid < FEB) mu[tid] = fma(qm, col[bf][tid], mu[tid]);
+        if (j == k + 1)
+#pragma unroll
+            for (int q = 0; q < 64; ++q) col[bf ^ 1][r0 + q] = S[q];
+        __syncthreads();
+    }
+    // Y = D - D G_new D with G_new(i, j) = (Sigma_new(i, j) - [i = j] d0_i t_i) / (t_i t_j) at the NEW t; r = delta - Y v
+    double* tn = col[0];
+    if (tid < FEB) {
+        const double w = pw[tid], b = pb[tid];
+        const double t = 1.0 / (1.0 + d0[tid] * w);
+        tn[tid] = t;
+        dd[tid] = w * t - dd[tid];
+        dl[tid] = t * b - dl[tid];
+        if (tid < nb) { wg[tid] = w; bg[tid] = b; }
+    }
+    __syncthreads();
+    if (tid < FEB) {                                                       // v = V_B' h + G delta  (old h, old G)
+        double a = vh[tid];
+        for (int q = 0; q < FEB; ++q) a = fma(G[tid + (long)q * FEB], dl[q], a);
+        vv[tid] = a;
+    }
+    __syncthreads();
+    const double Dj = dd[j], itj = 1.0 / tn[j];
+    double acc = 0.0;
+#pragma unroll
+    for (int q = 0; q < 64; ++q) {
+        const int i = r0 + q;
+        const double gn = (S[q] - (i == j ? d0[i] * tn[i] : 0.0)) / tn[i] * itj;
+        const double yv = (i == j ? dd[i] : 0.0) - dd[i] * gn * Dj;
+        Y[i + (long)j * FEB] = yv;
+        acc = fma(yv, vv[i], acc);                                         // (Y v)_j = sum_i Y(i, j) v_i  (Y symmetric)
+    }
+    part[half][j] = acc;
+    __syncthreads();
+    if (tid < FEB) r[tid] = dl[tid] - (part[0][tid] + part[1][tid]);
+}
+
+// h[i] += sum_q X(i, q) r[q]
+__global__ __launch_bounds__(256) void fitc_ep_hupdate_kernel(const double* __restrict__ X, long ldx, long nrows,
+                                                              const double* __restrict__ r, double* __restrict__ h) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nrows) return;
+    double a = 0.0;
+    for (int q = 0; q < FEB; ++q) a = fma(X[i + q * ldx], r[q], a);
+    h[i] += a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pgp_fitc_ep_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para, int flags, const double* xu, int64_t nu,
+                    const double* mvec, const double* dm, int nmean, int want, int warm, double* ttau_io, double* tnu_io,
+                    double* alpha_out, double* L_out, double* nlZ_out, double* dnlZ_out, int* sweeps_out,
+                    pgp_fitc** handle_out) {
+    if (!c) return -1;
+    GateShared device_gate_hold(c);
+    if (!c) return -1;
+    if (c->n <= 0) return -1;
+    if (!covhyp) return -3;
+    if (!xu || nu <= 0) return -8;
+    if (want < 1 || want > 3) return -11;
+    if (!ttau_io || !tnu_io) return -12;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->st;
+    const long n = c->n, d = c->d, np = c->np;
+    const int dpad = c->dpad;
+    const long nup = round_up(nu, 128);
+    CovSpec cs;
+    { const int rc = make_spec(c, kind, covhyp, ncov, para, flags, -1, d, cs); if (rc != PGP_OK) return rc == -11 ? -10 : rc; }
+    double kss = 0.0;
+    CHK(cov_point_value(c, cs, 2, &kss));
+    const double snu2 = 1e-6, isnu = 1.0 / sqrt(snu2);                    // lik.Erf has no hyper-parameter (inf.py:837-841)
+    const long ldf = 2 * nup + 128;
+    const size_t big = (size_t)nup * np * sizeof(double), sq = (size_t)nup * nup * sizeof(double);
+
+    PoolScratch tmp(c);
+    double *xud = nullptr, *XuT = nullptr, *Ku = nullptr, *V = nullptr, *Vs = nullptr, *U = nullptr, *F1 = nullptr, *F2 = nullptr,
+           *pack = nullptr, *vecs = nullptr, *nuv = nullptr, *part = nullptr, *Mm = nullptr, *X = nullptr, *Z = nullptr,
+           *Gb = nullptr, *Yb = nullptr, *blk = nullptr;
+    CHK(tmp.alloc(&xud, (size_t)nu * d * sizeof(double)));
+    CHK(tmp.alloc(&XuT, (size_t)dpad * nup * sizeof(double)));
+    CHK(tmp.alloc(&Ku, big)); CHK(tmp.alloc(&V, big)); CHK(tmp.alloc(&Vs, big)); CHK(tmp.alloc(&U, big));
+    CHK(tmp.alloc(&F1, (size_t)ldf * nup * sizeof(double)));
+    CHK(tmp.alloc(&F2, (size_t)ldf * nup * sizeof(double)));
+    CHK(tmp.alloc(&pack, (size_t)(nup / 128) * PACK_DOUBLES * sizeof(double)));
+    CHK(tmp.alloc(&vecs, (size_t)10 * np * sizeof(double)));
+    CHK(tmp.alloc(&nuv, (size_t)8 * nup * sizeof(double)));
+    CHK(tmp.alloc(&part, (size_t)std::max<long>(std::max<long>(32, (np + MV_CHUNK - 1) / MV_CHUNK) * nup, 1024) * sizeof(double)));
+    CHK(tmp.alloc(&Mm, sq));
+    CHK(tmp.alloc(&X, (size_t)nup * FEB * sizeof(double)));
+    CHK(tmp.alloc(&Z, (size_t)nup * FEB * sizeof(double)));
+    CHK(tmp.alloc(&Gb, (size_t)FEB * FEB * sizeof(double)));
+    CHK(tmp.alloc(&Yb, (size_t)FEB * FEB * sizeof(double)));
+    CHK(tmp.alloc(&blk, (size_t)2 * FEB * sizeof(double)));
+    double *cs_d = vecs, *sq_d = vecs + np, *tb_d = vecs + 2 * np, *vh_d = vecs + 3 * np, *tmp_d = vecs + 4 * np,
+           *w_d = vecs + 5 * np, *b_d = vecs + 6 * np, *d0_d = vecs + 7 * np, *m_d = vecs + 8 * np, *al_d = vecs + 9 * np;
+    double *be_d = nuv + nup, *h_d = nuv + 2 * nup, *alpha_d = nuv + 3 * nup, *wv_d = nuv + 4 * nup, *q_d = nuv + 5 * nup;
+    double *vhB = blk, *rB = blk + FEB;
+    HIP_TRY(hipMemsetAsync(vecs, 0, (size_t)10 * np * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(nuv, 0, (size_t)8 * nup * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(F1, 0, (size_t)ldf * nup * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(Ku, 0, big, st));
+    HIP_TRY(hipMemsetAsync(c->info_dev, 0, sizeof(int), st));
+
+    // ---- coordinates, Ku, Kuu, V, d0 (inf.py:835-848) ---------------------------------------------------------
+    HIP_TRY(hipMemcpyAsync(xud, xu, (size_t)nu * d * sizeof(double), hipMemcpyHostToDevice, st));
+    CHK(upload_scaled(c, c->x_dev, n, d, cs.scale, c->XsT, np, dpad, c->scale_dev));
+    CHK(scale_transpose_launch(xud, nu, (int)d, c->scale_dev, XuT, nup, dpad, st));
+    CHK(cov_rect_launch(c->XsT, np, n, XuT, nup, nu, dpad, cs, Ku, nup, st));
+    CHK(cov_factor_launch(XuT, nup, nu, nup, dpad, cs, 1.0 / snu2, F1, ldf, st));       // Kuu / snu2 + I
+    CHK(factor_with_inverse(c, F1, ldf, nup, pack));
+    double* E1 = F1 + nup + 128;
+    int info = 0;
+    HIP_TRY(hipMemcpyAsync(&info, c->info_dev, sizeof(int), hipMemcpyDeviceToHost, st));
+    CHK(gemm(c, E1, ldf, 1, Ku, nup, 1, V, nup, nup, np, nup, isnu, 0.0));               // V = Luu'^-1 Ku
+    CHK(colsumsq(V, nup, nup, np, cs_d, st));
+    std::vector<double> csum(n), yh(n), mh(n, 0.0);
+    HIP_TRY(hipMemcpyAsync(csum.data(), cs_d, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(yh.data(), c->y_dev, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (info != 0) return info > (int)nu ? (int)nu : info;
+    if (mvec) memcpy(mh.data(), mvec, n * sizeof(double));
+    std::vector<double> d0(n), w(n, 0.0), bb(n, 0.0), t(n), sv(n), sqs(n), tb(n), cu(n), vh(n), tau_n(n), nu_n(n);
+    for (long j = 0; j < n; ++j) d0[j] = kss - csum[j];                                   // inf.py:848
+    HIP_TRY(hipMemcpyAsync(d0_d, d0.data(), n * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(m_d, mh.data(), n * sizeof(double), hipMemcpyHostToDevice, st));
+
+    // ---- refresh (inf.py:257-275) + _epfitcZ (inf.py:235-255) from the host's (w, bb) --------------------------
+    double* E2 = F2 + nup + 128;
+    auto refresh = [&](double* nlZ) -> int {
+        for (long j = 0; j < n; ++j) {
+            t[j] = 1.0 / (1.0 + d0[j] * w[j]);
+            sv[j] = w[j] * t[j]; sqs[j] = sqrt(sv[j]); tb[j] = t[j] * bb[j];
+        }
+        HIP_TRY(hipMemcpyAsync(sq_d, sqs.data(), n * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(tb_d, tb.data(), n * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(w_d, w.data(), n * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(b_d, bb.data(), n * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(F2, 0, (size_t)ldf * nup * sizeof(double), st));
+        HIP_TRY(hipMemsetAsync(c->info_dev, 0, sizeof(int), st));
+        CHK(colscale(V, Vs, nup, nup, np, n, sq_d, st));                                 // Vs = V diag(sqrt s)
+        hipLaunchKernelGGL(set_diag_kernel, dim3((unsigned)((nup + 255) / 256)), dim3(256), 0, st, F2, ldf, nup, 1.0);
+        CHK(gemm(c, Vs, nup, 0, Vs, nup, 0, F2, ldf, nup, nup, np, 1.0, 1.0, 1));        // A = I + V diag(s) V'
+        CHK(matvec_rows(V, nup, nup, np, tb_d, 1.0, F2 + nup, ldf, part, st));           // rhs row: V (t o b)
+        CHK(factor_with_inverse(c, F2, ldf, nup, pack));
+        CHK(gather_strided_launch(F2 + nup, ldf, nup, be_d, st));                        // be = Lu'^-1 V (t o b)
+        CHK(logdet_ztz_launch(F2, ldf, nup, F2 + nup, ldf, c->scal, st));                // sum log diag(Lu), be'be
+        CHK(upper_matvec_launch(E2, ldf, nup, be_d, 1.0, part, h_d, st));                // h = M V (t o b)
+        CHK(gemm(c, E2, ldf, 0, E2, ldf, 0, Mm, nup, nup, nup, nup, 1.0, 0.0));          // M = E2 E2'
+        CHK(gemm(c, E2, ldf, 1, V, nup, 1, U, nup, nup, np, nup, 1.0, 0.0));             // U = E2' V
+        CHK(colsumsq(U, nup, nup, np, cs_d, st));                                        // diag(V'MV)
+        CHK(col_dot_full_launch(U, nup, nup, np, be_d, nullptr, vh_d, st));              // V'h = U' be
+        double sc2[2] = {0.0, 0.0};
+        HIP_TRY(hipMemcpyAsync(&info, c->info_dev, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(sc2, c->scal, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(cu.data(), cs_d, n * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(vh.data(), vh_d, n * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (info != 0) return info > (int)nu ? (int)nu : info;
+        if (!nlZ) return PGP_OK;
+        // ld = 2 sum log diag(Lu) + sum log(1 + d0 w)  ==  the reference's sum log(d0 + 1/w) + sum log w, finite at w = 0
+        double ld = 2.0 * sc2[0], slZ = 0.0, tst = sc2[1], s1 = 0.0, s2 = 0.0, s3 = 0.0;
+        for (long j = 0; j < n; ++j) {
+            const double ds = d0[j] * t[j] + t[j] * t[j] * cu[j];
+            const double mu = d0[j] * tb[j] + t[j] * vh[j];
+            tau_n[j] = 1.0 / ds - w[j];
+            nu_n[j] = mu / ds - bb[j] + mh[j] * tau_n[j];
+            double lZ;
+            erf_ep_moments(yh[j], nu_n[j] / tau_n[j], 1.0 / tau_n[j], &lZ, nullptr, nullptr);
+            slZ += lZ;
+            ld += log1p(d0[j] * w[j]);
+            tst += d0[j] * t[j] * bb[j] * bb[j];
+            const double e = nu_n[j] - mh[j] * tau_n[j];
+            s1 += e * ((w[j] / tau_n[j] * e - 2.0 * bb[j]) / (w[j] + tau_n[j]));
+            s2 += bb[j] * bb[j] / (tau_n[j] + w[j]);
+            s3 += log1p(w[j] / tau_n[j]);
+        }
+        *nlZ = 0.5 * ld - slZ - 0.5 * tst - 0.5 * s1 + 0.5 * s2 - 0.5 * s3;             // inf.py:250-253
+        return PGP_OK;
+    };
+
+    // ---- starting point (inf.py:855-870) ------------------------------------------------------------------------
+    double nlZ0 = 0.0;
+    for (long j = 0; j < n; ++j) {
+        double lZ;
+        erf_ep_moments(yh[j], mh[j], kss, &lZ, nullptr, nullptr);
+        nlZ0 -= lZ;
+    }
+    double nlZ = nlZ0;
+    if (warm) {
+        memcpy(w.data(), ttau_io, n * sizeof(double));
+        memcpy(bb.data(), tnu_io, n * sizeof(double));
+        CHK(refresh(&nlZ));
+        if (nlZ > nlZ0) {
+            std::fill(w.begin(), w.end(), 0.0); std::fill(bb.begin(), bb.end(), 0.0);
+            CHK(refresh(nullptr));
+            nlZ = nlZ0;
+        }
+    } else {
+        CHK(refresh(nullptr));
+    }
+
+    // ---- sweeps (inf.py:873-896) ----------------------------------------------------------------------------------
+    const double tol = 1e-4;
+    const int max_sweep = 10, min_sweep = 2;
+    double nlZ_old = INFINITY;
+    int sweep = 0;
+    const int nbl = (int)((n + FEB - 1) / FEB);
+    while ((fabs(nlZ - nlZ_old) > tol && sweep < max_sweep) || sweep < min_sweep) {
+        nlZ_old = nlZ;
+        ++sweep;
+        for (int b = 0; b < nbl; ++b) {
+            const long i0 = (long)b * FEB;
+            const int nb = (int)std::min<long>(FEB, n - i0);
+            const double* VB = V + i0 * nup;
+            CHK(gemm(c, Mm, nup, 0, VB, nup, 1, X, nup, nup, FEB, nup, 1.0, 0.0));        // X = M V_B
+            CHK(gemm(c, VB, nup, 1, X, nup, 1, Gb, FEB, FEB, FEB, nup, 1.0, 0.0));        // G = V_B' X
+            CHK(col_dot_full_launch(VB, nup, nup, FEB, h_d, nullptr, vhB, st));           // V_B' h
+            hipLaunchKernelGGL(fitc_ep_chain_kernel, dim3(1), dim3(256), 0, st, Gb, vhB, d0_d + i0, c->y_dev + i0, m_d + i0,
+                               w_d + i0, b_d + i0, nb, Yb, rB);
+            CHK(gemm(c, X, nup, 0, Yb, FEB, 1, Z, nup, nup, FEB, FEB, 1.0, 0.0));        // Z = X Y
+            CHK(gemm(c, Z, nup, 0, X, nup, 0, Mm, nup, nup, nup, FEB, -1.0, 1.0));       // M -= X Y X'
+            hipLaunchKernelGGL(fitc_ep_hupdate_kernel, dim3((unsigned)((nup + 255) / 256)), dim3(256), 0, st, X, nup, nup, rB,
+                               h_d);                                                      // h += X r
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(w.data(), w_d, n * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(bb.data(), b_d, n * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        CHK(refresh(&nlZ));                                                               // inf.py:895-896
+    }
+    if (sweeps_out) *sweeps_out = sweep;
+    memcpy(ttau_io, w.data(), n * sizeof(double));
+    memcpy(tnu_io, bb.data(), n * sizeof(double));
+
+    // ---- posterior (inf.py:902-908): alpha = Luu^-1 M V (t o b) = Luu^-1 h ;  L = E1 (E2 E2' - I) E1' / snu2 ------------
+    CHK(upper_matvec_launch(E1, ldf, nup, h_d, isnu, part, alpha_d, st));
+    double *M1 = nullptr, *Lp = nullptr;
+    CHK(tmp.alloc(&M1, sq)); CHK(tmp.alloc(&Lp, sq));
+    CHK(gemm(c, E1, ldf, 0, E2, ldf, 1, M1, nup, nup, nup, nup, 1.0, 0.0));
+    CHK(gemm(c, M1, nup, 0, M1, nup, 0, Lp, nup, nup, nup, nup, 1.0 / snu2, 0.0));
+    CHK(gemm(c, E1, ldf, 0, E1, ldf, 0, Lp, nup, nup, nup, nup, -1.0 / snu2, 1.0));
+    std::vector<double> alpha_h(nu);
+    HIP_TRY(hipMemcpyAsync(alpha_h.data(), alpha_d, nu * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (L_out) HIP_TRY(hipMemcpy2DAsync(L_out, nu * sizeof(double), Lp, nup * sizeof(double), nu * sizeof(double), nu,
+                                        hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (alpha_out) memcpy(alpha_out, alpha_h.data(), nu * sizeof(double));
+    if (nlZ_out) *nlZ_out = nlZ;
+
+    // ---- gradients (inf.py:910-942): FITC_Exact's pass with 1/g -> s and the long alpha al = t o b - s o V'h -----------
+    if (want >= 3 && dnlZ_out) {
+        double *Bm = nullptr, *W = nullptr, *R = nullptr, *dKuu = nullptr, *BW = nullptr, *RW = nullptr;
+        CHK(tmp.alloc(&Bm, big)); CHK(tmp.alloc(&W, big)); CHK(tmp.alloc(&R, big));
+        CHK(tmp.alloc(&dKuu, sq)); CHK(tmp.alloc(&BW, sq)); CHK(tmp.alloc(&RW, sq));
+        std::vector<double> al(n);
+        double sum_s = 0.0;
+        for (long j = 0; j < n; ++j) { al[j] = tb[j] - sv[j] * vh[j]; sum_s += sv[j]; }
+        HIP_TRY(hipMemcpyAsync(al_d, al.data(), n * sizeof(double), hipMemcpyHostToDevice, st));
+        CHK(gemm(c, E1, ldf, 0, V, nup, 1, Bm, nup, nup, np, nup, isnu, 0.0));           // B = iKuu Ku = Luu^-1 V
+        CHK(matvec_rows(Bm, nup, nup, np, al_d, 1.0, wv_d, 1, part, st));                // w = B al
+        double* Vg = Ku;                                                                 // Ku is no longer needed
+        CHK(colscale(Vs, Vg, nup, nup, np, n, sq_d, st));                                // V diag(s)
+        CHK(gemm(c, E2, ldf, 1, Vg, nup, 1, W, nup, nup, np, nup, 1.0, 0.0));            // W = Lu'^-1 V diag(s)
+        CHK(gemm(c, Bm, nup, 0, W, nup, 0, BW, nup, nup, nup, np, 1.0, 0.0));            // B W'
+        CHK(colsumsq(W, nup, nup, np, cs_d, st));
+        std::vector<double> cw(n), wv(nup), qv(nup), vcol(n);
+        HIP_TRY(hipMemcpyAsync(cw.data(), cs_d, n * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(wv.data(), wv_d, nup * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (int h = 0; h < ncov; ++h) {
+            CovSpec ch;
+            CHK(make_spec(c, kind, covhyp, ncov, para, flags, h, d, ch));
+            double dk0 = 0.0;
+            CHK(cov_point_value(c, ch, 2, &dk0));                                        // ddiagK
+            HIP_TRY(hipMemsetAsync(R, 0, big, st));
+            HIP_TRY(hipMemsetAsync(dKuu, 0, sq, st));
+            CHK(cov_rect_launch(c->XsT, np, n, XuT, nup, nu, dpad, ch, R, nup, st));     // dKu
+            CHK(cov_sym_launch(XuT, nup, nu, dpad, ch, dKuu, st, nup));                  // dKuu
+            CHK(gemm(c, dKuu, nup, 0, Bm, nup, 1, R, nup, nup, np, nup, -1.0, 2.0));     // R = 2 dKu - dKuu B  (= dA')
+            CHK(matvec_rows(R, nup, nup, np, al_d, 1.0, q_d, 1, part, st));              // R al
+            CHK(coldot2(R, Bm, nup, nup, np, dk0, tmp_d, st));                           // v = ddiagK - diag(dQ)
+            CHK(gemm(c, R, nup, 0, W, nup, 0, RW, nup, nup, nup, np, 1.0, 0.0));         // R W'
+            HIP_TRY(hipMemcpyAsync(qv.data(), q_d, nup * sizeof(double), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(vcol.data(), tmp_d, n * sizeof(double), hipMemcpyDeviceToHost, st));
+            double rwbw = 0.0;
+            CHK(dot_host(c, RW, BW, nup * nup, part, &rwbw));
+            double wq = 0.0, s3 = 0.0, s4 = 0.0;
+            for (long i = 0; i < nu; ++i) wq += wv[i] * qv[i];
+            for (long j = 0; j < n; ++j) { s3 += vcol[j] * al[j] * al[j]; s4 += cw[j] * vcol[j]; }
+            dnlZ_out[nmean + h] = 0.5 * (dk0 * sum_s - wq - s3 - s4 - rwbw);             // inf.py:917-923
+        }
+        for (int i = 0; i < nmean; ++i) {                                                // inf.py:937-941, final cavities
+            double s = 0.0;
+            for (long j = 0; j < n; ++j) {
+                double lZ, dlZ;
+                erf_ep_moments(yh[j], nu_n[j] / tau_n[j], 1.0 / tau_n[j], &lZ, &dlZ, nullptr);
+                s += dm[(long)i * n + j] * dlZ;
+            }
+            dnlZ_out[i] = -s;
+        }
+    }
+    if (handle_out) {
+        pgp_fitc* f = new pgp_fitc();
+        f->nu = nu; f->nup = nup; f->d = (int)d; f->dpad = dpad; f->cs = cs; f->kss = kss;
+        CHK(spool_take(c, (size_t)dpad * nup * sizeof(double), (void**)&f->XuT));
+        CHK(spool_take(c, nup * sizeof(double), (void**)&f->alpha));
+        CHK(spool_take(c, (size_t)nup * nup * sizeof(double), (void**)&f->Lpost));
+        HIP_TRY(hipMemcpyAsync(f->XuT, XuT, (size_t)dpad * nup * sizeof(double), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(f->alpha, alpha_d, nup * sizeof(double), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(f->Lpost, Lp, sq, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        *handle_out = f;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    if (c->prof) prof_collect(c);
+    return PGP_OK;
 }
 
 }  // extern "C"

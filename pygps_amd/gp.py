@@ -281,3 +281,23 @@ class GPR_FITC(GP_FITC):
 
     def useInference(self, newInf):
         raise Exception('FITC_Laplace / FITC_EP are out of scope of pygps_amd.')
+
+
+class GPC_FITC(GP_FITC):
+    """Sparse binary GP classification with the FITC approximation (Core/gp.py:1117-1235): Zero mean, RBF, Erf
+    likelihood, FITC_EP inference, Minimize."""
+
+    def __init__(self):
+        super(GPC_FITC, self).__init__()
+        self.meanfunc = mean.Zero()
+        self.covfunc = cov.RBF()
+        self.likfunc = lik.Erf()
+        self.inffunc = inf.FITC_EP()
+        self.optimizer = opt.Minimize(self)
+        self.u = None
+
+    def useInference(self, newInf):
+        """The reference accepts only 'Laplace' here (Core/gp.py:1192-1202), i.e. FITC_Laplace, which is not built."""
+        if newInf == "Laplace":
+            raise NotImplementedError("pygps_amd: FITC_Laplace (GPC_FITC.useInference('Laplace')) is not implemented")
+        raise Exception('Possible inf values are "Laplace".')

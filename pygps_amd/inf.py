@@ -640,3 +640,75 @@ class FITC_Exact(Inference):
                 return post, nlz, dnlZ
             return post, nlz
         return post
+
+
+class FITC_EP(Inference):
+    """FITC-EP approximation to the posterior GP (Core/inf.py:810-944): EP with lik.Erf on Kt = Q + diag(K - Q),
+    Q = Ku' inv(Kuu + snu2 I) Ku, snu2 = 1e-6 (Erf has no noise hyper-parameter, inf.py:837-841).  One device call
+    (csrc/fitc.hip, pgp_fitc_ep_fit): 128-site block sweeps in O(n nu) memory.  ``last_ttau`` / ``last_tnu`` persist across
+    calls and warm-start the next one as the reference's do (inf.py:857-870); ones of another length start cold.
+    ``sweeps``: EP sweeps of the last call.
+
+    One deviation: at 10 sweeps this logs the warning "maximum number of sweeps reached" as inf.EP does, where the reference
+    raises AttributeError (FITC_EP.__init__ never sets self.logger, inf.py:823-826)."""
+
+    def __init__(self):
+        self.name = 'FITC Expectation Propagation'
+        self.last_ttau = None
+        self.last_tnu = None
+        self.device = None
+        self.sweeps = 0
+
+    def evaluate(self, meanfunc, covfunc, likfunc, x, y, nargout=1):
+        if not isinstance(covfunc, _cov.FITCOfKernel):
+            raise NotImplementedError("pygps_amd: FITC_EP needs a FITC covariance (covfunc.fitc(u)); only covFITC is supported")
+        if not isinstance(likfunc, _lik.Erf):
+            raise NotImplementedError("pygps_amd: FITC_EP runs on the device for lik.Erf only (no CPU fallback)")
+        dev = _lib.default_device() if self.device is None else self.device
+        kind, para, flags = _device_kernel(covfunc.covfunc, _lib.ctx(dev))
+        x = _lib.f64(x)
+        n, D = x.shape
+        xu = _lib.f64(covfunc.inducingInput)
+        if xu.shape[1] != D:
+            raise Exception('Dimensionality of inducing inputs must match training inputs')
+        nu = xu.shape[0]
+        y = _lib.f64(y).reshape(n)
+        _Resident.ensure(x, y, dev)
+        m, dm, nm = _mean_inputs(meanfunc, x)
+        hyp = _lib.f64(np.asarray(covfunc.hyp, dtype=float))
+        nc = len(hyp)
+        warm = (self.last_ttau is not None and self.last_tnu is not None
+                and np.asarray(self.last_ttau).size == n and np.asarray(self.last_tnu).size == n)
+        ttau = _lib.f64(np.asarray(self.last_ttau, dtype=float)).reshape(n).copy() if warm else np.zeros(n)
+        tnu = _lib.f64(np.asarray(self.last_tnu, dtype=float)).reshape(n).copy() if warm else np.zeros(n)
+        alpha = np.empty(nu)
+        Lm = np.empty((nu, nu))
+        nlZ = np.zeros(1)
+        g = np.zeros(nm + nc)
+        sweeps = C.c_int()
+        fh = C.c_void_p()
+        rc = _lib.load().pgp_fitc_ep_fit(_lib.ctx(dev), kind, _lib.ptr(hyp), nc, int(para), int(flags), _lib.ptr(xu), nu,
+                                         _lib.ptr(m), _lib.ptr(dm), nm, int(min(max(nargout, 1), 3)), int(warm),
+                                         _lib.ptr(ttau), _lib.ptr(tnu), _lib.ptr(alpha), _lib.ptr(Lm), _lib.ptr(nlZ),
+                                         _lib.ptr(g), C.byref(sweeps), C.byref(fh))
+        _lib.check(rc, "pgp_fitc_ep_fit")
+        self.sweeps = sweeps.value
+        if self.sweeps == 10:
+            logging.getLogger(__name__).warning("maximum number of sweeps reached in function infEP")
+        self.last_ttau = ttau.reshape(n, 1)                     # inf.py:899-900
+        self.last_tnu = tnu.reshape(n, 1)
+        post = postStruct()
+        post.alpha = alpha.reshape(nu, 1)
+        post.L = Lm                                       # -R0'V inv(Kt + diag(1/ttau)) V'R0: dense, not triangular (inf.py:908)
+        post.sW = np.sqrt(ttau).reshape(n, 1)             # inf.py:902
+        post.fitc = FITCPosterior(fh, dev, _lib.current_slot())
+        if nargout > 1:
+            nlz = np.float64(nlZ[0])
+            if nargout > 2:
+                dnlZ = dnlZStruct(meanfunc, covfunc, likfunc)
+                dnlZ.mean = [np.float64(v) for v in g[:nm]]
+                dnlZ.cov = [np.float64(v) for v in g[nm:nm + nc]]
+                dnlZ.lik = []
+                return post, nlz, dnlZ
+            return post, nlz
+        return post
