@@ -133,6 +133,21 @@ int pgp_ep_fit_dense(pgp_ctx* ctx, const double* K, const double* mvec, const do
                      double* ttau_io, double* tnu_io, double* alpha_out, double* sW_out, double* nlZ_out,
                      double* dnlZ_mean_out, int* sweeps_out, pgp_factor** factor_out);
 
+/* EP.evaluate with a likelihood argument (lik, likhyp, nlik as pgp_laplace_fit): PGP_LIK_ERF (nlik = 0: the fit of pgp_ep_fit /
+ * pgp_ep_fit_dense) or PGP_LIK_LAPLACE (nlik = 1, likhyp = [log sn]: lik.Laplace, Core/lik.py:370-512).  dnlZ_out: nmean + ncov + 1
+ * entries (mean, cov, lik; the dense form: nmean + 1, the covariance gradients follow from pgp_dense_grad_term as after
+ * pgp_ep_fit_dense).  dnlZ.lik = -sum dlZhyp over the cavities (Core/inf.py:796-798).  With lik.Laplace the mean and likelihood
+ * gradients are evaluated at the cavity of f (nu_n / tau_n + m); ref_compat = 1 evaluates them at the reference's nu_n / tau_n,
+ * which differs wherever the mean is not zero.  A bad (lik, likhyp, nlik) returns -15.  Other arguments and status codes as
+ * pgp_ep_fit. */
+int pgp_ep_fit_lik(pgp_ctx* ctx, int kind, const double* covhyp, int ncov, int para, int flags, int lik, const double* likhyp,
+                   int nlik, int ref_compat, const double* mvec, const double* dm, int nmean, int want, int warm, double* ttau_io,
+                   double* tnu_io, double* alpha_out, double* sW_out, double* nlZ_out, double* dnlZ_out, int* sweeps_out,
+                   pgp_factor** factor_out);
+int pgp_ep_fit_dense_lik(pgp_ctx* ctx, const double* K, int lik, const double* likhyp, int nlik, int ref_compat, const double* mvec,
+                         const double* dm, int nmean, int want, int warm, double* ttau_io, double* tnu_io, double* alpha_out,
+                         double* sW_out, double* nlZ_out, double* dnlZ_out, int* sweeps_out, pgp_factor** factor_out);
+
 /* ---- Laplace.evaluate with lik.Erf or lik.Gauss (Core/inf.py:459-564; Core/lik.py:175-197, 274-293) -----------------------
  * The Newton iteration in f with Brent's line search (inf.py:466-512, tools.py:121-272: tol 1e-6, at most 20 steps, s in [0, 2],
  * at most 20 evaluations per line search, thr 1e-4), then the posterior (inf.py:514-529) and, for want = 3, the gradients with
@@ -145,6 +160,7 @@ int pgp_ep_fit_dense(pgp_ctx* ctx, const double* K, const double* mvec, const do
  * occur for Erf or Gauss).  Other status codes as pgp_ep_fit. */
 #define PGP_LIK_ERF 0
 #define PGP_LIK_GAUSS 1
+#define PGP_LIK_LAPLACE 2  /* EP only (pgp_ep_fit_lik, pgp_ep_fit_dense_lik) */
 #define PGP_ERR_LAPLACE_WNEG (-90)
 int pgp_laplace_fit(pgp_ctx* ctx, int kind, const double* covhyp, int ncov, int para, int flags, int lik, const double* likhyp,
                     int nlik, const double* mvec, const double* dm, int nmean, int want, int warm, double* alpha_io,
@@ -180,6 +196,15 @@ int pgp_fitc_ep_fit(pgp_ctx* ctx, int kind, const double* covhyp, int ncov, int 
                     const double* mvec, const double* dm, int nmean, int want, int warm, double* ttau_io, double* tnu_io,
                     double* alpha_out, double* L_out, double* nlZ_out, double* dnlZ_out, int* sweeps_out,
                     pgp_fitc** handle_out);
+/* FITC_EP with a likelihood argument (lik, likhyp, nlik as pgp_ep_fit_lik): PGP_LIK_ERF (nlik = 0: the fit of pgp_fitc_ep_fit) or
+ * PGP_LIK_LAPLACE (nlik = 1, likhyp = [log sn]; snu2 = 1e-6 sn2, inf.py:837-841).  dnlZ_out: nmean + ncov + 1 entries with
+ * lik.Laplace (mean, cov, lik), nmean + ncov with lik.Erf.  dnlZ.lik = -sum dlZhyp + snu2 (covariance-like term), inf.py:925-936,
+ * with dlZhyp at the cavity nu_n / tau_n; ref_compat = 1 evaluates it at the reference's nu_n / tau_n + m, which counts the
+ * mean twice.  A bad (lik, likhyp, nlik) returns -15.  Other arguments and status codes as pgp_fitc_ep_fit. */
+int pgp_fitc_ep_fit_lik(pgp_ctx* ctx, int kind, const double* covhyp, int ncov, int para, int flags, int lik, const double* likhyp,
+                        int nlik, int ref_compat, const double* xu, int64_t nu, const double* mvec, const double* dm, int nmean,
+                        int want, int warm, double* ttau_io, double* tnu_io, double* alpha_out, double* L_out, double* nlZ_out,
+                        double* dnlZ_out, int* sweeps_out, pgp_fitc** handle_out);
 
 /* ---- ONE fit over the GPUs of a node (no reference counterpart: Core/inf.py:353-384 runs on one host) ---
  * One process per GPU, every rank calls with the same data (pgp_set_data) and arguments.  The factorisation is 1-D

@@ -22,7 +22,7 @@ PROG_LEAF, PROG_SUM, PROG_PRODUCT, PROG_SCALE = 1, 2, 3, 4
 PROG_MAX_ARD_DIM = 64             # input dimensions of the (single) ARD leaf of a device program
 PROG_MAX = 8                      # leaves / Scale nodes / products per device program (csrc/sqdist_tile.h)
 MODE_TRAIN, MODE_CROSS, MODE_SELF_TEST = 0, 1, 2
-LIK_ERF, LIK_GAUSS = 0, 1
+LIK_ERF, LIK_GAUSS, LIK_LAPLACE = 0, 1, 2
 ERR_LAPLACE_WNEG = -90
 FLAG_MATERN_REFERENCE_DER = 1
 STAGES = ("assemble", "potrf", "solve", "trtri", "lauum", "grad", "total")
@@ -56,6 +56,10 @@ SIGNATURES = {
                              _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int), C.POINTER(_vp)]),
     "pgp_ep_fit_dense": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp,
                                    C.POINTER(C.c_int), C.POINTER(_vp)]),
+    "pgp_ep_fit_lik": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp,
+                                 C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int), C.POINTER(_vp)]),
+    "pgp_ep_fit_dense_lik": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp,
+                                       _dp, _dp, _dp, _dp, C.POINTER(C.c_int), C.POINTER(_vp)]),
     "pgp_laplace_fit": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int,
                                   C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.POINTER(C.c_int), _dp, C.POINTER(_vp)]),
     "pgp_laplace_fit_dense": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp,
@@ -66,6 +70,9 @@ SIGNATURES = {
     "pgp_fitc_free": (None, [_vp, _vp]),
     "pgp_fitc_ep_fit": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _i64, _dp, _dp, C.c_int, C.c_int,
                                   C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int), C.POINTER(_vp)]),
+    "pgp_fitc_ep_fit_lik": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _dp, _i64,
+                                      _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int),
+                                      C.POINTER(_vp)]),
     "pgp_potrf": (C.c_int, [_vp, _dp, _i64, _dp]),
     "pgp_potrs": (C.c_int, [_vp, _dp, _i64, _dp, _i64, _dp]),
     "pgp_last_timings": (C.c_int, [_vp, _dp]),
@@ -102,6 +109,7 @@ TEST_SIGNATURES = {
                                           C.POINTER(C.c_int)]),
     "pgp_test_probit_hazard": (C.c_int, [_vp, _dp, _dp, C.c_int]),
     "pgp_test_laplace_lik": (C.c_int, [_vp, C.c_int, C.c_double, _dp, _dp, C.c_int, _dp]),
+    "pgp_test_laplace_ep_lik": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_int, _dp]),
     "pgp_test_valu_peak": (C.c_int, [_vp, C.c_int, C.c_int, _dp]),
     "pgp_test_mfma_peak": (C.c_int, [_vp, C.c_int, _dp]),
     "pgp_test_mfma_cycles": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp]),

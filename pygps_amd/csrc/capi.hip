@@ -208,6 +208,8 @@ int pgp_set_option(pgp_ctx* c, const char* name, int value) {
     if (!strcmp(name, "gram_assembly")) { if (value < 0 || value > 2) return -2; c->gram_assembly = value; return PGP_OK; }
     if (!strcmp(name, "yield")) { c->yield = value; return PGP_OK; }
     if (!strcmp(name, "ep_fused")) { c->ep_fused = value; return PGP_OK; }
+    if (!strcmp(name, "ep_tol_exp")) { if (value < 1 || value > 16) return -3; c->ep_tol_exp = value; return PGP_OK; }
+    if (!strcmp(name, "ep_max_sweep")) { if (value < 2 || value > 1000) return -3; c->ep_max_sweep = value; return PGP_OK; }
     if (!strcmp(name, "laplace_tol_exp")) { if (value < 1 || value > 16) return -3; c->laplace_tol_exp = value; return PGP_OK; }
     if (!strcmp(name, "ep_r_direct")) { c->ep_r_direct = value; return PGP_OK; }
     if (!strcmp(name, "ep_alpha_direct")) { c->ep_alpha_direct = value; return PGP_OK; }

@@ -107,6 +107,8 @@ struct pgp_ctx {
     int ep_final_rebuild = 0;           // EP, carried posterior: 1 = _epComputeParams once more on the converged site parameters and everything
                                         // returned comes from it (round 3); 0 = alpha / nlZ / gradients from the carried Sigma, mu, log det B
                                         // and ONE plain Cholesky for post.L
+    int ep_tol_exp = 4;                 // EP: the sweeps stop once nlZ changes by at most 10^-ep_tol_exp (inf.py:732: 1e-4)
+    int ep_max_sweep = 10;              // EP: at most this many sweeps (inf.py:732: 10)
     int laplace_tol_exp = 6;            // Laplace: the Newton iteration stops once Psi decreases by less than 10^-laplace_tol_exp (inf.py:467)
     int ep_sigma_under = 1;             // EP: Sigma = K - V'V'^T accumulated under the sweep of the parameter recomputation (ep_fused 2)
     int ep_wait_kernel = 1;             // EP block sweep: the bulk stream waits for the chain in a one-wave kernel of its own (1) or inside

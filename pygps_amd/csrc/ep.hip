@@ -1,5 +1,5 @@
-// Expectation propagation for the probit likelihood on the device -- reference: Core/inf.py EP.evaluate
-// :731-806, Inference._epComputeParams :174-189, Core/lik.py Erf (EP mode) :295-366.
+// Expectation propagation for the probit and the Laplacian likelihood on the device -- reference: Core/inf.py EP.evaluate
+// :731-806, Inference._epComputeParams :174-189, Core/lik.py Erf (EP mode) :295-366, Laplace (EP mode) :432-512.
 //
 // The site loop is inherently sequential (site i+1 needs Sigma_ii, mu_i after site i's update, fixed order 0..n-1,
 // inf.py:757).  Two forms:
@@ -28,6 +28,7 @@
 
 #include "ctx.h"
 #include "erf_lik.h"
+#include "laplace_lik.h"
 #include "erfcx_poly.h"
 
 namespace {
@@ -48,11 +49,18 @@ __device__ __forceinline__ double block_sum(double v, double* red /* 4 doubles *
     return red[0] + red[1] + red[2] + red[3];
 }
 
+// EP-mode moments of the fit's likelihood: lik.Erf (no hyper-parameter) or lik.Laplace (sn = exp(hyp[0]))
+__device__ __forceinline__ void ep_lik_moments(int lik, double sn, double y, double mu, double s2, double* lZ, double* dlZ,
+                                               double* d2lZ) {
+    if (lik == PGP_LIK_LAPLACE) laplace_ep_moments(y, mu, s2, sn, lZ, dlZ, d2lZ);
+    else erf_ep_moments(y, mu, s2, lZ, dlZ, d2lZ);
+}
+
 __global__ __launch_bounds__(256) void ep_site_kernel(const double* __restrict__ Sig, long ld, long np, long i,
                                                       const double* __restrict__ mu, const double* __restrict__ m,
                                                       const double* __restrict__ y, double* __restrict__ ttau,
                                                       double* __restrict__ tnu, double* __restrict__ sbuf,
-                                                      double* __restrict__ coef) {
+                                                      double* __restrict__ coef, int lik, double sn) {
     const long r = (long)blockIdx.x * 256 + threadIdx.x;
     if (r < np) sbuf[r] = Sig[r + i * ld];
     if (r == 0) {
@@ -60,7 +68,7 @@ __global__ __launch_bounds__(256) void ep_site_kernel(const double* __restrict__
         const double tau_ni = 1.0 / sii - ttau[i];                         // cavity (inf.py:759-760)
         const double nu_ni = mu[i] / sii + m[i] * tau_ni - tnu[i];
         double lZ, dlZ, d2lZ;
-        erf_ep_moments(y[i], nu_ni / tau_ni, 1.0 / tau_ni, &lZ, &dlZ, &d2lZ);
+        ep_lik_moments(lik, sn, y[i], nu_ni / tau_ni, 1.0 / tau_ni, &lZ, &dlZ, &d2lZ);
         const double ttau_old = ttau[i];
         double t_new = -d2lZ / (1.0 + d2lZ / tau_ni);
         t_new = fmax(t_new, 0.0);                                          // inf.py:765
@@ -235,6 +243,23 @@ __device__ __forceinline__ void ep_site_update(double sii, double mui, double tp
     EpSiteMid h;
     ep_site_update_a(sii, mui, tp, np_, mi, yi, h);
     ep_site_update_b(sii, mui, tp, np_, mi, h, t_new, nu_new, cj, qj);
+}
+// The same site update for lik.Laplace (inf.py:759-769 + lik.py:450-487), written as the reference's scalar arithmetic: IEEE
+// divisions and the library's erf / log / exp -- the moments combine two log Phi terms in log space, which leaves nothing to
+// trim the way the probit fraction above is trimmed.
+__device__ __forceinline__ void ep_site_update_laplace(double sii, double mui, double tp, double np_, double mi, double yi, double sn,
+                                                       double& t_new, double& nu_new, double& cj, double& qj) {
+    const double tau_ni = 1.0 / sii - tp;                              // cavity (inf.py:759-760)
+    const double nu_ni = mui / sii + mi * tau_ni - np_;
+    double lZ, dlZ, d2lZ;
+    laplace_ep_moments(yi, nu_ni / tau_ni, 1.0 / tau_ni, sn, &lZ, &dlZ, &d2lZ);
+    const double den = 1.0 + d2lZ / tau_ni;
+    t_new = fmax(-d2lZ / den, 0.0);                                    // inf.py:764-765
+    nu_new = (dlZ + (mi - nu_ni / tau_ni) * d2lZ) / den;
+    const double ds2 = t_new - tp;
+    cj = ds2 / (1.0 + ds2 * sii);                                      // inf.py:769
+    const double dnu = nu_new - np_;
+    qj = dnu - cj * fma(dnu, sii, mui);                                // mu_new = mu + Sigma(:, k) qj
 }
 
 // ---- block sweep (round 3) ---------------------------------------------------------------------------------
@@ -435,12 +460,13 @@ __device__ __forceinline__ void ep_prep_body(int blk, double* Sig, long ld, long
 // replaced by these counters but still one launch per block 21.2; resident with release / acquire fences 21.1; with agent-scope
 // loads and stores 20.7.  (The body of a block as a non-inlined function: callee-saved registers in scratch, site loop 14 % slower:
 // 24.0.  One loop over the blocks AROUND the roles instead of one inside each: 636 bytes of spills.)
-template <bool TIMED>                            // TIMED: s_memtime stamps and spin counts of block 5 (PGP_EP_TIMING); costs registers
+// LIK: the likelihood of the site updates (PGP_LIK_ERF or PGP_LIK_LAPLACE with noise sn); nothing but wave 0's site update depends on it
+template <bool TIMED, int LIK>                   // TIMED: s_memtime stamps and spin counts of block 5 (PGP_EP_TIMING); costs registers
 __global__ __launch_bounds__(512) void ep_chain_kernel(double* Sig, long ld, long n, int nbl, double* mu, const double* __restrict__ m,
                                                         const double* __restrict__ y, double* ttau, double* tnu, double* Wbuf,
                                                         double* gbuf, double* ldbuf, unsigned* yield_flags, long long* stamps_b5,
                                                         double* Sbuf, double* Tile, unsigned* flags, unsigned cbase, unsigned pbase,
-                                                        unsigned sbase, unsigned swg) {
+                                                        unsigned sbase, unsigned swg, double sn) {
     extern __shared__ __attribute__((aligned(32))) double ep_smem[];
     if (blockIdx.x > 0) {
         if (threadIdx.x < 256) {
@@ -519,7 +545,8 @@ __global__ __launch_bounds__(512) void ep_chain_kernel(double* Sig, long ld, lon
                 const int kn = k + 1 < EPB ? k + 1 : EPB - 1;
                 const double pn0 = prm[kn][0], pn1 = prm[kn][1], pn2 = prm[kn][2], pn3 = prm[kn][3];
                 double t_new, nu_new, cj, qj;
-                ep_site_update(dkk, muk, pc0, pc1, pc2, pc3, t_new, nu_new, cj, qj);
+                if constexpr (LIK == PGP_LIK_LAPLACE) ep_site_update_laplace(dkk, muk, pc0, pc1, pc2, pc3, sn, t_new, nu_new, cj, qj);
+                else ep_site_update(dkk, muk, pc0, pc1, pc2, pc3, t_new, nu_new, cj, qj);
                 fprod *= fma(t_new - pc0, dkk, 1.0);
                 if ((k & 31) == 31) { lsum += log(fprod); fprod = 1.0; }
                 if (lane == 0) {
@@ -885,11 +912,13 @@ __global__ __launch_bounds__(256) void ep_build_kernel(const double* __restrict_
 // Per-site terms of the EP marginal likelihood (inf.py:184-188) and, optionally, d lZ_i / d mu (inf.py:788-790) on the device:
 // the host loop over n sites (probit moments in double, ~0.3 us each) sat between every sweep and the next one -- 1.2 ms of
 // idle GPU per parameter recomputation at N = 4096.  Block partials [blk][5] = (sum lZ, t3, t4, t5, t6) in a fixed order.
+// lik / sn: the likelihood (ep_lik_moments); dhyp (lik.Laplace only, optional): d lZ_i / d log sn at the same cavity (inf.py:796-798).
 __global__ __launch_bounds__(256) void ep_site_terms_kernel(long n, const double* __restrict__ y, const double* __restrict__ m,
                                                             const double* __restrict__ mu, const double* __restrict__ dsig,
                                                             double dsig_const, const double* __restrict__ ttau,
                                                             const double* __restrict__ tnu, int with_m,
-                                                            double* __restrict__ partial, double* __restrict__ dlz) {
+                                                            double* __restrict__ partial, double* __restrict__ dlz,
+                                                            int lik, double sn, double* __restrict__ dhyp) {
     __shared__ double red[4];
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
@@ -899,8 +928,9 @@ __global__ __launch_bounds__(256) void ep_site_terms_kernel(long n, const double
         const double tau_n = 1.0 / ds - tt;
         const double nu_n = mui / ds - tn + (with_m ? m[i] * tau_n : 0.0);
         double lZ, dl;
-        erf_ep_moments(y[i], nu_n / tau_n, 1.0 / tau_n, &lZ, &dl, nullptr);
+        ep_lik_moments(lik, sn, y[i], nu_n / tau_n, 1.0 / tau_n, &lZ, &dl, nullptr);
         if (dlz) dlz[i] = dl;
+        if (dhyp) dhyp[i] = laplace_ep_dlZhyp(y[i], nu_n / tau_n, 1.0 / tau_n, sn);
         const double a = nu_n - (with_m ? m[i] * tau_n : 0.0);
         v[0] = lZ;
         v[1] = tn * mui;
@@ -942,6 +972,8 @@ struct EpWork {
     double* tile;                        // block sweep: Sigma_BB, mu_B, diag Sigma_BB as the prep workgroups hand them to the chain
     unsigned* flags;                     // EPF_*: the device counters through which the resident sweep kernel and the bulk stream meet
     unsigned chain_total, prep_total, strip_total;   // their values once everything launched so far has run (strips in launches)
+    int lik;                             // PGP_LIK_ERF or PGP_LIK_LAPLACE
+    double sn;                           // lik.Laplace: exp(hyp[0])
 };
 
 }  // namespace
@@ -1034,7 +1066,7 @@ static int ep_compute_params(pgp_ctx* c, EpWork& w, const std::vector<double>& y
     const long nblk_terms = (n + 255) / 256;
     std::vector<double> part_h(5 * nblk_terms);
     hipLaunchKernelGGL(ep_site_terms_kernel, dim3((unsigned)nblk_terms), dim3(256), 0, st, n, c->y_dev, w.m_d, w.mu_d, w.diag_d, 0.0,
-                       w.ttau_d, w.tnu_d, 1, w.tmp_d, (double*)nullptr);
+                       w.ttau_d, w.tnu_d, 1, w.tmp_d, (double*)nullptr, w.lik, w.sn, (double*)nullptr);
     HIP_TRY(hipMemcpyAsync(part_h.data(), w.tmp_d, part_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     double sc[2];
     HIP_TRY(hipMemcpyAsync(mu_h.data(), w.mu_d, n * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1118,7 +1150,7 @@ static int ep_wait_failed(const unsigned* eflags, unsigned chain_total, unsigned
 static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double* covhyp, int ncov, int para, int flags,
                        const double* mvec, const double* dm, int nmean, int want, int warm, double* ttau_io, double* tnu_io,
                        double* alpha_out, double* sW_out, double* nlZ_out, double* dnlZ_out, int* sweeps_out,
-                       pgp_factor** factor_out) {
+                       pgp_factor** factor_out, int lik = PGP_LIK_ERF, double sn = 0.0, int ref_compat = 0) {
     if (!c) return -1;
     if (c->n <= 0) return -1;
     if (!covhyp && !Kdense) return -3;
@@ -1161,6 +1193,7 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
     };
     EpWork w{};
     w.n = n; w.np = np; w.ldf = ldf;
+    w.lik = lik; w.sn = sn;
     const size_t nn = (size_t)np * np * sizeof(double);
     // RAII: every early return (HIP_TRY / EP_TRY / CHK) gives the scratch back to the context's pool, scrubs + returns the
     // factor buffer and frees a half-built handle -- no hipMalloc / hipFree (device-synchronising) on the steady-state path
@@ -1213,7 +1246,7 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
         if (dense) EP_TRY(gather_strided_launch(w.Kd, np + 1, np, w.diag_d, st));          // K_ii differs from point to point
         hipLaunchKernelGGL(ep_site_terms_kernel, dim3((unsigned)nbt), dim3(256), 0, st, n, c->y_dev, w.m_d, (const double*)nullptr,
                            dense ? (const double*)w.diag_d : (const double*)nullptr, kdiag, (const double*)nullptr, (const double*)nullptr,
-                           1, w.tmp_d, (double*)nullptr);
+                           1, w.tmp_d, (double*)nullptr, lik, sn, (double*)nullptr);
         HIP_TRY(hipMemcpyAsync(ph.data(), w.tmp_d, ph.size() * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         for (long b = 0; b < nbt; ++b) nlZ0 -= ph[5 * b];
@@ -1247,8 +1280,8 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
     }
     HIP_TRY(hipStreamSynchronize(st));
     stamp("K built, nlZ0", 0);
-    const double tol = 1e-4;
-    const int max_sweep = 10, min_sweep = 2;
+    const double tol = c->ep_tol_exp == 4 ? 1e-4 : pow(10.0, -c->ep_tol_exp);     // options ep_tol_exp / ep_max_sweep: gradient checks
+    const int max_sweep = c->ep_max_sweep, min_sweep = 2;
     double nlZ_old = INFINITY;
     int sweep = 0;
     // ONE block sweep per device at a time, and nothing else of this process beside it (ctx.h DeviceGate: the sweep is a resident
@@ -1288,14 +1321,13 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
             HIP_TRY(hipEventRecord(c->ep_ev[0], st));
             if (sa != st) HIP_TRY(hipStreamWaitEvent(sa, c->ep_ev[0], 0));
             if (sa == st) return PGP_ERR_HIP;          // (the resident kernel needs a stream of its own beside the bulk launches)
-            if (ep_timing)
-                hipLaunchKernelGGL(ep_chain_kernel<true>, dim3(37), dim3(512), EP_BLOCK_LDS, sa, w.Sig, np, n, (int)nbl, w.mu_d, w.m_d,
-                                   c->y_dev, w.ttau_d, w.tnu_d, w.Wb, w.gb, w.ldb, yfl, (long long*)(w.gb + 2 * EPB), w.S, w.tile, w.flags,
-                                   w.chain_total, w.prep_total, w.strip_total, swg);
-            else
-                hipLaunchKernelGGL(ep_chain_kernel<false>, dim3(37), dim3(512), EP_BLOCK_LDS, sa, w.Sig, np, n, (int)nbl, w.mu_d, w.m_d,
-                                   c->y_dev, w.ttau_d, w.tnu_d, w.Wb, w.gb, w.ldb, yfl, (long long*)nullptr, w.S, w.tile, w.flags,
-                                   w.chain_total, w.prep_total, w.strip_total, swg);
+            {
+                auto kern = lik == PGP_LIK_LAPLACE ? (ep_timing ? ep_chain_kernel<true, PGP_LIK_LAPLACE> : ep_chain_kernel<false, PGP_LIK_LAPLACE>)
+                                                   : (ep_timing ? ep_chain_kernel<true, PGP_LIK_ERF> : ep_chain_kernel<false, PGP_LIK_ERF>);
+                hipLaunchKernelGGL(kern, dim3(37), dim3(512), EP_BLOCK_LDS, sa, w.Sig, np, n, (int)nbl, w.mu_d, w.m_d,
+                                   c->y_dev, w.ttau_d, w.tnu_d, w.Wb, w.gb, w.ldb, yfl, ep_timing ? (long long*)(w.gb + 2 * EPB) : (long long*)nullptr,
+                                   w.S, w.tile, w.flags, w.chain_total, w.prep_total, w.strip_total, swg, sn);
+            }
             HIP_TRY(hipEventRecord(c->ep_ev[1], sa));
             // from here on the resident kernel is spinning on device counters: an early return (a failed launch on the bulk stream)
             // must stop it and wait for it before the scratch it reads and writes goes back to the pool
@@ -1378,7 +1410,7 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
         } else
         for (long i = 0; i < n; ++i) {
             hipLaunchKernelGGL(ep_site_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, w.Sig, np, np, i,
-                               w.mu_d, w.m_d, c->y_dev, w.ttau_d, w.tnu_d, w.sbuf, w.coef);
+                               w.mu_d, w.m_d, c->y_dev, w.ttau_d, w.tnu_d, w.sbuf, w.coef, lik, sn);
             hipLaunchKernelGGL(ep_rank1_mu_kernel, dim3((unsigned)((np + 3) / 4)), dim3(256), 0, st, w.Sig, np, np,
                                w.sbuf, w.coef, w.tnu_d, w.mu_d);
         }
@@ -1399,7 +1431,7 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
             const double* const res_h = c->res_host + (w.ldb - c->res_dev);
             EP_TRY(gather_strided_launch(w.Sig, np + 1, np, w.diag_d, st));
             hipLaunchKernelGGL(ep_site_terms_kernel, dim3((unsigned)nbt), dim3(256), 0, st, n, c->y_dev, w.m_d, w.mu_d, w.diag_d, 0.0,
-                               w.ttau_d, w.tnu_d, 1, part_d, (double*)nullptr);
+                               w.ttau_d, w.tnu_d, 1, part_d, (double*)nullptr, lik, sn, (double*)nullptr);
             if (merge12 && sweep == 1 && 2 * res_slot <= np) {
                 HIP_TRY(hipMemcpyAsync(w.ldb + res_slot, w.ldb, (size_t)res_len * sizeof(double), hipMemcpyDeviceToDevice, st));
                 deferred = true;
@@ -1523,20 +1555,30 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
         std::vector<double> g(ncov + 1, 0.0);
         if (!dense) HIP_TRY(hipMemcpyAsync(g.data(), c->scal + 8, (ncov + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        if (nmean > 0) {                              // d lZ_j / d mu on the device (inf.py:788-790: no m term in nu_n), dot with dm on the host
-            std::vector<double> dl(n);
+        const bool laplace = lik == PGP_LIK_LAPLACE;
+        double dlik = 0.0;
+        if (nmean > 0 || laplace) {
+            // d lZ_j / d mu on the device, dot with dm on the host.  lik.Erf: the reference's point (inf.py:788-790: no m term in
+            // nu_n).  lik.Laplace: the cavity of f itself, nu_n / tau_n + m -- the reference's point is off by m wherever the mean is
+            // not zero (GPR's default mean is Const(mean(y))); ref_compat 1 evaluates dlZhyp there as the reference does
+            // (inf.py:796-798).  With it, d lZ_j / d log sn (inf.py:796-798) for dnlZ.lik.
+            const int with_m = laplace && !ref_compat ? 1 : 0;
+            std::vector<double> dl(n), dh(laplace ? n : 0);
             hipLaunchKernelGGL(ep_site_terms_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, c->y_dev, w.m_d, w.mu_d,
-                               w.diag_d, 0.0, w.ttau_d, w.tnu_d, 0, w.tmp_d, w.sbuf);
+                               w.diag_d, 0.0, w.ttau_d, w.tnu_d, with_m, w.tmp_d, w.sbuf, lik, sn, laplace ? w.coef : (double*)nullptr);
             HIP_TRY(hipMemcpyAsync(dl.data(), w.sbuf, n * sizeof(double), hipMemcpyDeviceToHost, st));
+            if (laplace) HIP_TRY(hipMemcpyAsync(dh.data(), w.coef, n * sizeof(double), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             for (int i = 0; i < nmean; ++i) {
                 double sacc = 0.0;
                 for (long j = 0; j < n; ++j) sacc += dl[j] * dm[(long)i * n + j];
                 dnlZ_out[i] = -sacc;
             }
+            if (laplace)
+                for (long j = 0; j < n; ++j) dlik -= dh[j];
         }
         for (int h = 0; h < ncov; ++h) dnlZ_out[nmean + h] = 0.5 * g[h];
-        dnlZ_out[nmean + ncov] = 0.0;                                                   // lik.Erf has no hyper
+        dnlZ_out[nmean + ncov] = dlik;                                                  // 0 for lik.Erf: no hyper
     }
     if (c->prof) prof_collect(c);
     HIP_TRY(hipStreamSynchronize(st));
@@ -1589,4 +1631,37 @@ extern "C" int pgp_ep_fit_dense(pgp_ctx* c, const double* K, const double* mvec,
     if (!K) return -2;
     return ep_fit_core(c, K, 0, nullptr, 0, 0, 0, mvec, dm, nmean, want, warm, ttau_io, tnu_io, alpha_out, sW_out, nlZ_out,
                        dnlZ_mean_out, sweeps_out, factor_out);
+}
+
+// EP with a likelihood argument (lik, likhyp, nlik as pgp_laplace_fit): PGP_LIK_ERF (nlik 0; the same fit as pgp_ep_fit) or
+// PGP_LIK_LAPLACE (nlik 1, likhyp = [log sn]).  dnlZ_out = [mean.., cov.., lik].  ref_compat (lik.Laplace): evaluate the gradients
+// at the reference's point nu_n / tau_n (inf.py:788-798), not at the cavity of f.
+static int ep_lik_args(int lik, const double* likhyp, int nlik, double* sn) {
+    if (lik == PGP_LIK_ERF) { if (nlik != 0) return -15; *sn = 0.0; return PGP_OK; }
+    if (lik != PGP_LIK_LAPLACE) return -15;
+    if (nlik != 1 || !likhyp) return -15;
+    *sn = exp(likhyp[0]);
+    return PGP_OK;
+}
+
+extern "C" int pgp_ep_fit_lik(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para, int flags, int lik, const double* likhyp,
+                              int nlik, int ref_compat, const double* mvec, const double* dm, int nmean, int want, int warm,
+                              double* ttau_io, double* tnu_io, double* alpha_out, double* sW_out, double* nlZ_out, double* dnlZ_out,
+                              int* sweeps_out, pgp_factor** factor_out) {
+    if (!covhyp) return -3;
+    double sn = 0.0;
+    CHK(ep_lik_args(lik, likhyp, nlik, &sn));
+    return ep_fit_core(c, nullptr, kind, covhyp, ncov, para, flags, mvec, dm, nmean, want, warm, ttau_io, tnu_io, alpha_out, sW_out,
+                       nlZ_out, dnlZ_out, sweeps_out, factor_out, lik, sn, ref_compat);
+}
+
+extern "C" int pgp_ep_fit_dense_lik(pgp_ctx* c, const double* K, int lik, const double* likhyp, int nlik, int ref_compat,
+                                    const double* mvec, const double* dm, int nmean, int want, int warm, double* ttau_io,
+                                    double* tnu_io, double* alpha_out, double* sW_out, double* nlZ_out, double* dnlZ_out,
+                                    int* sweeps_out, pgp_factor** factor_out) {
+    if (!K) return -2;
+    double sn = 0.0;
+    CHK(ep_lik_args(lik, likhyp, nlik, &sn));
+    return ep_fit_core(c, K, 0, nullptr, 0, 0, 0, mvec, dm, nmean, want, warm, ttau_io, tnu_io, alpha_out, sW_out, nlZ_out,
+                       dnlZ_out, sweeps_out, factor_out, lik, sn, ref_compat);
 }

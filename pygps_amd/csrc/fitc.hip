@@ -18,6 +18,7 @@
 
 #include "ctx.h"
 #include "erf_lik.h"
+#include "laplace_lik.h"
 
 struct pgp_fitc {
     long nu = 0, nup = 0;
@@ -472,13 +473,20 @@ namespace {
 
 constexpr int FEB = 128;                       // sites per block
 
+// EP-mode moments of the fit's likelihood, host and device: lik.Erf or lik.Laplace (noise sn)
+__host__ __device__ inline void fitc_lik_moments(int lik, double sn, double y, double mu, double s2, double* lZ, double* dlZ,
+                                                 double* d2lZ) {
+    if (lik == PGP_LIK_LAPLACE) laplace_ep_moments(y, mu, s2, sn, lZ, dlZ, d2lZ);
+    else erf_ep_moments(y, mu, s2, lZ, dlZ, d2lZ);
+}
+
 // lZ, dlZ, d2lZ -> new site parameters (inf.py:879-890; the same scalar update as dense EP, inf.py:759-767)
-__device__ __forceinline__ void fitc_ep_site(double sii, double mui, double w, double b, double m, double y, double& w_new,
-                                             double& b_new) {
+__device__ __forceinline__ void fitc_ep_site(double sii, double mui, double w, double b, double m, double y, int lik, double sn,
+                                             double& w_new, double& b_new) {
     const double tau_ni = 1.0 / sii - w;
     const double nu_ni = mui / sii + m * tau_ni - b;
     double lZ, dlZ, d2lZ;
-    erf_ep_moments(y, nu_ni / tau_ni, 1.0 / tau_ni, &lZ, &dlZ, &d2lZ);
+    fitc_lik_moments(lik, sn, y, nu_ni / tau_ni, 1.0 / tau_ni, &lZ, &dlZ, &d2lZ);
     w_new = fmax(-d2lZ / (1.0 + d2lZ / tau_ni), 0.0);
     b_new = (dlZ + (m - nu_ni / tau_ni) * d2lZ) / (1.0 + d2lZ / tau_ni);
 }
@@ -490,7 +498,7 @@ __global__ __launch_bounds__(256) void fitc_ep_chain_kernel(const double* __rest
                                                             const double* __restrict__ d0g, const double* __restrict__ yg,
                                                             const double* __restrict__ mg, double* __restrict__ wg,
                                                             double* __restrict__ bg, int nb, double* __restrict__ Y,
-                                                            double* __restrict__ r) {
+                                                            double* __restrict__ r, int lik, double sn) {
     __shared__ double col[2][FEB], mu[FEB], d0[FEB], tt[FEB], dd[FEB], dl[FEB], vv[FEB], part[2][FEB];
     __shared__ double pw[FEB], pb[FEB], pm[FEB], py[FEB], cq[2];
     const int tid = threadIdx.x, j = tid & (FEB - 1), half = tid >> 7, r0 = 64 * half;
@@ -521,7 +529,7 @@ __global__ __launch_bounds__(256) void fitc_ep_chain_kernel(const double* __rest
         if (tid == 0) {
             const double sii = col[bf][k], mui = mu[k], w = pw[k], b = pb[k];
             double w_new, b_new;
-            fitc_ep_site(sii, mui, w, b, pm[k], py[k], w_new, b_new);
+            fitc_ep_site(sii, mui, w, b, pm[k], py[k], lik, sn, w_new, b_new);
             const double ds2 = w_new - w, dn = b_new - b;
             const double c = ds2 / (1.0 + ds2 * sii);                        // Sigma -= c s s'  (inf.py:769)
             cq[0] = c;
@@ -584,10 +592,11 @@ __global__ __launch_bounds__(256) void fitc_ep_hupdate_kernel(const double* __re
 
 extern "C" {
 
-int pgp_fitc_ep_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para, int flags, const double* xu, int64_t nu,
-                    const double* mvec, const double* dm, int nmean, int want, int warm, double* ttau_io, double* tnu_io,
-                    double* alpha_out, double* L_out, double* nlZ_out, double* dnlZ_out, int* sweeps_out,
-                    pgp_fitc** handle_out) {
+// lik: PGP_LIK_ERF or PGP_LIK_LAPLACE with log_sn = its hyp[0]; ref_compat: dnlZ.lik at the reference's point (see below)
+static int fitc_ep_core(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para, int flags, const double* xu, int64_t nu,
+                        const double* mvec, const double* dm, int nmean, int want, int warm, double* ttau_io, double* tnu_io,
+                        double* alpha_out, double* L_out, double* nlZ_out, double* dnlZ_out, int* sweeps_out,
+                        pgp_fitc** handle_out, int lik, double log_sn, int ref_compat) {
     if (!c) return -1;
     GateShared device_gate_hold(c);
     if (!c) return -1;
@@ -605,7 +614,10 @@ int pgp_fitc_ep_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int pa
     { const int rc = make_spec(c, kind, covhyp, ncov, para, flags, -1, d, cs); if (rc != PGP_OK) return rc == -11 ? -10 : rc; }
     double kss = 0.0;
     CHK(cov_point_value(c, cs, 2, &kss));
-    const double snu2 = 1e-6, isnu = 1.0 / sqrt(snu2);                    // lik.Erf has no hyper-parameter (inf.py:837-841)
+    // inducing-input noise (inf.py:837-841): 1e-6 sn2 with a likelihood hyper-parameter, 1e-6 without (lik.Erf)
+    const bool laplace = lik == PGP_LIK_LAPLACE;
+    const double sn = laplace ? exp(log_sn) : 0.0;
+    const double snu2 = laplace ? 1.e-6 * exp(2.0 * log_sn) : 1e-6, isnu = 1.0 / sqrt(snu2);
     const long ldf = 2 * nup + 128;
     const size_t big = (size_t)nup * np * sizeof(double), sq = (size_t)nup * nup * sizeof(double);
 
@@ -702,7 +714,7 @@ int pgp_fitc_ep_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int pa
             tau_n[j] = 1.0 / ds - w[j];
             nu_n[j] = mu / ds - bb[j] + mh[j] * tau_n[j];
             double lZ;
-            erf_ep_moments(yh[j], nu_n[j] / tau_n[j], 1.0 / tau_n[j], &lZ, nullptr, nullptr);
+            fitc_lik_moments(lik, sn, yh[j], nu_n[j] / tau_n[j], 1.0 / tau_n[j], &lZ, nullptr, nullptr);
             slZ += lZ;
             ld += log1p(d0[j] * w[j]);
             tst += d0[j] * t[j] * bb[j] * bb[j];
@@ -719,7 +731,7 @@ int pgp_fitc_ep_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int pa
     double nlZ0 = 0.0;
     for (long j = 0; j < n; ++j) {
         double lZ;
-        erf_ep_moments(yh[j], mh[j], kss, &lZ, nullptr, nullptr);
+        fitc_lik_moments(lik, sn, yh[j], mh[j], kss, &lZ, nullptr, nullptr);
         nlZ0 -= lZ;
     }
     double nlZ = nlZ0;
@@ -737,8 +749,8 @@ int pgp_fitc_ep_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int pa
     }
 
     // ---- sweeps (inf.py:873-896) ----------------------------------------------------------------------------------
-    const double tol = 1e-4;
-    const int max_sweep = 10, min_sweep = 2;
+    const double tol = c->ep_tol_exp == 4 ? 1e-4 : pow(10.0, -c->ep_tol_exp);     // options ep_tol_exp / ep_max_sweep: gradient checks
+    const int max_sweep = c->ep_max_sweep, min_sweep = 2;
     double nlZ_old = INFINITY;
     int sweep = 0;
     const int nbl = (int)((n + FEB - 1) / FEB);
@@ -753,7 +765,7 @@ int pgp_fitc_ep_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int pa
             CHK(gemm(c, VB, nup, 1, X, nup, 1, Gb, FEB, FEB, FEB, nup, 1.0, 0.0));        // G = V_B' X
             CHK(col_dot_full_launch(VB, nup, nup, FEB, h_d, nullptr, vhB, st));           // V_B' h
             hipLaunchKernelGGL(fitc_ep_chain_kernel, dim3(1), dim3(256), 0, st, Gb, vhB, d0_d + i0, c->y_dev + i0, m_d + i0,
-                               w_d + i0, b_d + i0, nb, Yb, rB);
+                               w_d + i0, b_d + i0, nb, Yb, rB, lik, sn);
             CHK(gemm(c, X, nup, 0, Yb, FEB, 1, Z, nup, nup, FEB, FEB, 1.0, 0.0));        // Z = X Y
             CHK(gemm(c, Z, nup, 0, X, nup, 0, Mm, nup, nup, nup, FEB, -1.0, 1.0));       // M -= X Y X'
             hipLaunchKernelGGL(fitc_ep_hupdate_kernel, dim3((unsigned)((nup + 255) / 256)), dim3(256), 0, st, X, nup, nup, rB,
@@ -830,10 +842,29 @@ int pgp_fitc_ep_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int pa
             double s = 0.0;
             for (long j = 0; j < n; ++j) {
                 double lZ, dlZ;
-                erf_ep_moments(yh[j], nu_n[j] / tau_n[j], 1.0 / tau_n[j], &lZ, &dlZ, nullptr);
+                fitc_lik_moments(lik, sn, yh[j], nu_n[j] / tau_n[j], 1.0 / tau_n[j], &lZ, &dlZ, nullptr);
                 s += dm[(long)i * n + j] * dlZ;
             }
             dnlZ_out[i] = -s;
+        }
+        if (laplace) {
+            // dnlZ.lik (inf.py:925-936): -sum dlZhyp at the final cavities, plus the "covariance-like" term of snu2 = 1e-6 sn2:
+            //   snu2 (||RVdd R0tV'||^2 - sum colsum(RVdd^2) o v + post.alpha' post.alpha - sum alpha^2 o v),  v = colsum(R0tV^2)
+            // read here as R0tV = B, RVdd ~ W (W'W = RVdd'RVdd), the long alpha = al, post.alpha = B al = w.  The reference
+            // evaluates dlZhyp at nu_n / tau_n + m, but _epfitcZ's nu_n already carries m tau_n (inf.py:248): the mean counts
+            // twice (central differences agree with nu_n / tau_n).  ref_compat 1 reproduces the reference's point.
+            CHK(colsumsq(Bm, nup, nup, np, cs_d, st));
+            std::vector<double> vb(n);
+            HIP_TRY(hipMemcpyAsync(vb.data(), cs_d, n * sizeof(double), hipMemcpyDeviceToHost, st));
+            double bwbw = 0.0;
+            CHK(dot_host(c, BW, BW, nup * nup, part, &bwbw));
+            double dh = 0.0, z = bwbw;
+            for (long i = 0; i < nu; ++i) z += wv[i] * wv[i];
+            for (long j = 0; j < n; ++j) {
+                z -= cw[j] * vb[j] + al[j] * al[j] * vb[j];
+                dh += laplace_ep_dlZhyp(yh[j], nu_n[j] / tau_n[j] + (ref_compat ? mh[j] : 0.0), 1.0 / tau_n[j], sn);
+            }
+            dnlZ_out[nmean + ncov] = -dh + snu2 * z;
         }
     }
     if (handle_out) {
@@ -851,6 +882,24 @@ int pgp_fitc_ep_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int pa
     HIP_TRY(hipStreamSynchronize(st));
     if (c->prof) prof_collect(c);
     return PGP_OK;
+}
+
+int pgp_fitc_ep_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para, int flags, const double* xu, int64_t nu,
+                    const double* mvec, const double* dm, int nmean, int want, int warm, double* ttau_io, double* tnu_io,
+                    double* alpha_out, double* L_out, double* nlZ_out, double* dnlZ_out, int* sweeps_out,
+                    pgp_fitc** handle_out) {
+    return fitc_ep_core(c, kind, covhyp, ncov, para, flags, xu, nu, mvec, dm, nmean, want, warm, ttau_io, tnu_io, alpha_out, L_out,
+                        nlZ_out, dnlZ_out, sweeps_out, handle_out, PGP_LIK_ERF, 0.0, 0);
+}
+
+int pgp_fitc_ep_fit_lik(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para, int flags, int lik, const double* likhyp,
+                        int nlik, int ref_compat, const double* xu, int64_t nu, const double* mvec, const double* dm, int nmean,
+                        int want, int warm, double* ttau_io, double* tnu_io, double* alpha_out, double* L_out, double* nlZ_out,
+                        double* dnlZ_out, int* sweeps_out, pgp_fitc** handle_out) {
+    if (lik == PGP_LIK_ERF) { if (nlik != 0) return -15; }
+    else if (lik != PGP_LIK_LAPLACE || nlik != 1 || !likhyp) return -15;
+    return fitc_ep_core(c, kind, covhyp, ncov, para, flags, xu, nu, mvec, dm, nmean, want, warm, ttau_io, tnu_io, alpha_out, L_out,
+                        nlZ_out, dnlZ_out, sweeps_out, handle_out, lik, lik == PGP_LIK_LAPLACE ? likhyp[0] : 0.0, ref_compat);
 }
 
 }  // extern "C"

@@ -21,6 +21,8 @@ int pgp_test_probit_hazard(pgp_ctx* ctx, const double* z, double* out, int n);
 /* the Laplace-mode likelihood derivatives of the device (csrc/erf_lik.h) at host (y, f): out (4, n) rows lp, dlp, d2lp, d3lp.
    lik: PGP_LIK_ERF or PGP_LIK_GAUSS (log_sn used for Gauss only) */
 int pgp_test_laplace_lik(pgp_ctx* ctx, int lik, double log_sn, const double* y, const double* f, int n, double* out);
+/* lik.Laplace, EP mode (csrc/laplace_lik.h) on the device at host (y, mu, s2, sn) per site: out (4, n) rows lZ, dlZ, d2lZ, dlZhyp. */
+int pgp_test_laplace_ep_lik(pgp_ctx* ctx, const double* y, const double* mu, const double* s2, const double* sn, int n, double* out);
 int pgp_test_valu_peak(pgp_ctx* ctx, int iters, int waves_per_simd, double* out2);
 int pgp_test_mfma_peak(pgp_ctx* ctx, int iters, double* tflops_out);
 int pgp_test_mfma_cycles(pgp_ctx* ctx, int iters, int nacc, int waves_per_simd, double* out3);

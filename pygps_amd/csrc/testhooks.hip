@@ -11,6 +11,7 @@
 
 #include "testhooks.h"
 #include "erf_lik.h"
+#include "laplace_lik.h"
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
@@ -736,6 +737,34 @@ extern "C" int pgp_test_laplace_lik(pgp_ctx* c, int lik, double log_sn, const do
     HIP_TRY(hipMemcpy(yd, y, (size_t)n * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(fd, f, (size_t)n * 8, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(laplace_lik_test_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->st, lik, exp(2.0 * log_sn), yd, fd, od, n);
+    HIP_TRY(hipStreamSynchronize(c->st));
+    HIP_TRY(hipMemcpy(out, od, (size_t)4 * n * 8, hipMemcpyDeviceToHost));
+    return PGP_OK;
+}
+
+namespace {
+__global__ void laplace_ep_lik_test_kernel(const double* __restrict__ in, double* __restrict__ out, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double y = in[i], mu = in[n + i], s2 = in[2L * n + i], sn = in[3L * n + i];
+    double lZ, dlZ, d2lZ;
+    laplace_ep_moments(y, mu, s2, sn, &lZ, &dlZ, &d2lZ);
+    out[i] = lZ; out[n + i] = dlZ; out[2L * n + i] = d2lZ; out[3L * n + i] = laplace_ep_dlZhyp(y, mu, s2, sn);
+}
+}  // namespace
+
+// self-test hook: lik.Laplace's EP-mode moments and dlZhyp (csrc/laplace_lik.h) on the device, rows lZ, dlZ, d2lZ, dlZhyp of out (4, n)
+extern "C" int pgp_test_laplace_ep_lik(pgp_ctx* c, const double* y, const double* mu, const double* s2, const double* sn, int n,
+                                       double* out) {
+    if (!c || !y || !mu || !s2 || !sn || !out || n <= 0) return -1;
+    HIP_TRY(hipSetDevice(c->device));
+    DevScratch scr;
+    double *id, *od;
+    CHK(scr.alloc(&id, (size_t)4 * n * 8)); CHK(scr.alloc(&od, (size_t)4 * n * 8));
+    const double* src[4] = {y, mu, s2, sn};
+    for (int q = 0; q < 4; ++q) HIP_TRY(hipMemcpy(id + (size_t)q * n, src[q], (size_t)n * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(laplace_ep_lik_test_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->st, id, od, n);
+    HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->st));
     HIP_TRY(hipMemcpy(out, od, (size_t)4 * n * 8, hipMemcpyDeviceToHost));
     return PGP_OK;

@@ -207,6 +207,14 @@ class GPR(GP):
         else:
             raise Exception('Possible inf values are "Laplace", "EP".')
 
+    def useLikelihood(self, newLik):
+        """'Laplace': lik.Laplace with EP inference (Core/gp.py:624-635)."""
+        if newLik == "Laplace":
+            self.likfunc = lik.Laplace()
+            self.inffunc = inf.EP()
+        else:
+            raise Exception('Possible lik values are "Laplace".')
+
 
 class GPC(GP):
     """Binary GP classification: Zero mean, RBF, Erf likelihood, EP inference, Minimize."""
@@ -281,6 +289,14 @@ class GPR_FITC(GP_FITC):
 
     def useInference(self, newInf):
         raise Exception('FITC_Laplace / FITC_EP are out of scope of pygps_amd.')
+
+    def useLikelihood(self, newLik):
+        """'Laplace': lik.Laplace with FITC_EP inference (Core/gp.py:1104-1114)."""
+        if newLik == "Laplace":
+            self.likfunc = lik.Laplace()
+            self.inffunc = inf.FITC_EP()
+        else:
+            raise Exception('Possible lik values are "Laplace".')
 
 
 class GPC_FITC(GP_FITC):

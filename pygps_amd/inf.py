@@ -364,9 +364,16 @@ class Exact(Inference):
 
 
 class EP(Inference):
-    """Expectation propagation with the probit likelihood (Core/inf.py:723-806).  The site-parameter
+    """Expectation propagation with the probit likelihood or lik.Laplace (Core/inf.py:723-806).  The site-parameter
     state (last_ttau / last_tnu) persists on the object across calls and warm-starts the next one,
-    exactly like the reference."""
+    exactly like the reference.
+
+    Both likelihoods run through pgp_ep_fit_lik (pgp_ep_fit_dense_lik for covariance trees that are not device programs).
+    With lik.Laplace the mean and likelihood gradients are evaluated at the cavity of f, nu_n / tau_n + m; the reference
+    evaluates them at nu_n / tau_n (inf.py:788-798), which is off by m wherever the mean is not zero, and takes the first
+    site's dlZ for every site in the mean gradient.  ``reference_compat = True`` moves both, dnlZ.lik and the mean gradient,
+    to the reference's point nu_n / tau_n (the mean gradient stays per site).  lik.Erf keeps the reference's point for its
+    mean gradient whatever this flag says: that is what the G8 / G14 recordings pin."""
 
     def __init__(self):
         self.name = "Expectation Propagation"
@@ -374,11 +381,21 @@ class EP(Inference):
         self.last_tnu = None
         self.device = None
         self.sweeps = 0
+        self.reference_compat = False
+        self._tol_exp = None            # private: sweep tolerance 10^-_tol_exp instead of the reference's 1e-4 (gradient checks)
 
     def evaluate(self, meanfunc, covfunc, likfunc, x, y, nargout=1):
-        if not isinstance(likfunc, _lik.Erf):
-            raise NotImplementedError("pygps_amd: EP runs on the device for lik.Erf only (no CPU fallback)")
+        if isinstance(likfunc, _lik.Laplace):
+            lik, likhyp = _lib.LIK_LAPLACE, _lib.f64(np.asarray(likfunc.hyp, dtype=float).reshape(-1))
+        elif isinstance(likfunc, _lik.Erf):
+            lik, likhyp = _lib.LIK_ERF, None
+        else:
+            raise NotImplementedError("pygps_amd: EP runs on the device for lik.Erf and lik.Laplace only (no CPU fallback)")
+        nlik = 0 if likhyp is None else 1
         dev = _lib.default_device() if self.device is None else self.device
+        # covariance functions that are not device programs (Core/cov.py:230-328 composes anything): K and the derivative
+        # matrices come from getCovMatrix / getDerMatrix, the sweeps, the posterior, alpha, nlZ and every Hadamard sum
+        # 1/2 sum((sW sW' o B^-1 - alpha alpha') o dK_h) (Core/inf.py:780-786) run on the device
         dense = isinstance(covfunc, _cov._Composite) and not covfunc._on_device()
         if not dense:
             kind, para, flags = _device_kernel(covfunc, _lib.ctx(dev))
@@ -389,9 +406,7 @@ class EP(Inference):
         _Resident.ensure(x, y, dev)
         m, dm, nm = _mean_inputs(meanfunc, x)
         hyp = _lib.f64(np.asarray(covfunc.hyp, dtype=float))
-        nc = len(hyp)
-        if dense:
-            return self._evaluate_dense(meanfunc, covfunc, likfunc, x, n, m, dm, nm, nc, dev, nargout)
+        nc = 0 if dense else len(hyp)
         warm = self.last_ttau is not None
         ttau = _lib.f64(self.last_ttau).reshape(n).copy() if warm else np.zeros(n)
         tnu = _lib.f64(self.last_tnu).reshape(n).copy() if warm else np.zeros(n)
@@ -401,52 +416,32 @@ class EP(Inference):
         g = np.zeros(nm + nc + 1)
         sweeps = C.c_int()
         fh = C.c_void_p()
-        rc = _lib.load().pgp_ep_fit(_lib.ctx(dev), kind, _lib.ptr(hyp), nc, int(para), int(flags), _lib.ptr(m),
-                                    _lib.ptr(dm), nm, int(min(max(nargout, 1), 3)), int(warm), _lib.ptr(ttau),
-                                    _lib.ptr(tnu), _lib.ptr(alpha), _lib.ptr(sW), _lib.ptr(nlZ), _lib.ptr(g),
-                                    C.byref(sweeps), C.byref(fh))
-        if rc == -99:
-            raise NotImplementedError("pygps_amd: the device EP path is not built in this version")
-        _lib.check(rc, "pgp_ep_fit")
-        self.sweeps = sweeps.value
-        if self.sweeps == 10:
-            logging.getLogger(__name__).warning("maximum number of sweeps reached in function infEP")
-        self.last_ttau = ttau.reshape(n, 1)
-        self.last_tnu = tnu.reshape(n, 1)
-        post = postStruct()
-        post.alpha = alpha.reshape(n, 1)
-        post.sW = sW.reshape(n, 1)
-        post.L = DeviceFactor(fh, n, dev, _lib.current_slot())
-        if nargout > 2:
-            dnlZ = dnlZStruct(meanfunc, covfunc, likfunc)
-            dnlZ.mean = [np.float64(v) for v in g[:nm]]
-            dnlZ.cov = [np.float64(v) for v in g[nm:nm + nc]]
-            dnlZ.lik = []
-            return post, np.float64(nlZ[0]), dnlZ
-        return post, np.float64(nlZ[0])
-
-
-    def _evaluate_dense(self, meanfunc, covfunc, likfunc, x, n, m, dm, nm, nc, dev, nargout):
-        """Covariance functions that are not device programs (Core/cov.py:230-328 composes anything): K and the derivative
-        matrices come from getCovMatrix / getDerMatrix, the site sweeps, the posterior, alpha, nlZ and every Hadamard sum
-        1/2 sum((sW sW' o B^-1 - alpha alpha') o dK_h) (Core/inf.py:780-786) run on the device."""
+        want = int(min(max(nargout, 1), 3))
         lib = _lib.load()
         ctx = _lib.ctx(dev)
-        K = _lib.f64(covfunc.getCovMatrix(x=x, mode="train"))
-        warm = self.last_ttau is not None
-        ttau = _lib.f64(self.last_ttau).reshape(n).copy() if warm else np.zeros(n)
-        tnu = _lib.f64(self.last_tnu).reshape(n).copy() if warm else np.zeros(n)
-        alpha = np.empty(n)
-        sW = np.empty(n)
-        nlZ = np.zeros(1)
-        g = np.zeros(nm + 1)
-        sweeps = C.c_int()
-        fh = C.c_void_p()
-        want = int(min(max(nargout, 1), 3))
-        _lib.check(lib.pgp_ep_fit_dense(ctx, _lib.ptr(K), _lib.ptr(m), _lib.ptr(dm), nm, want, int(warm), _lib.ptr(ttau),
-                                        _lib.ptr(tnu), _lib.ptr(alpha), _lib.ptr(sW), _lib.ptr(nlZ), _lib.ptr(g),
-                                        C.byref(sweeps), C.byref(fh)), "pgp_ep_fit_dense")
-        del K
+        compat = int(bool(self.reference_compat))
+        lh = _lib.ptr(likhyp) if nlik else None
+        if self._tol_exp is not None:
+            _lib.check(lib.pgp_set_option(ctx, b"ep_tol_exp", int(self._tol_exp)), "pgp_set_option")
+            _lib.check(lib.pgp_set_option(ctx, b"ep_max_sweep", 1000), "pgp_set_option")
+        try:
+            if dense:
+                K = _lib.f64(covfunc.getCovMatrix(x=x, mode="train"))
+                rc = lib.pgp_ep_fit_dense_lik(ctx, _lib.ptr(K), lik, lh, nlik, compat, _lib.ptr(m), _lib.ptr(dm), nm, want,
+                                              int(warm), _lib.ptr(ttau), _lib.ptr(tnu), _lib.ptr(alpha), _lib.ptr(sW),
+                                              _lib.ptr(nlZ), _lib.ptr(g), C.byref(sweeps), C.byref(fh))
+                del K
+            else:
+                rc = lib.pgp_ep_fit_lik(ctx, kind, _lib.ptr(hyp), nc, int(para), int(flags), lik, lh, nlik, compat, _lib.ptr(m),
+                                        _lib.ptr(dm), nm, want, int(warm), _lib.ptr(ttau), _lib.ptr(tnu), _lib.ptr(alpha),
+                                        _lib.ptr(sW), _lib.ptr(nlZ), _lib.ptr(g), C.byref(sweeps), C.byref(fh))
+        finally:
+            if self._tol_exp is not None:
+                lib.pgp_set_option(ctx, b"ep_tol_exp", 4)
+                lib.pgp_set_option(ctx, b"ep_max_sweep", 10)
+        if rc == -99:
+            raise NotImplementedError("pygps_amd: the device EP path is not built in this version")
+        _lib.check(rc, "pgp_ep_fit_dense_lik" if dense else "pgp_ep_fit_lik")
         self.sweeps = sweeps.value
         if self.sweeps == 10:
             logging.getLogger(__name__).warning("maximum number of sweeps reached in function infEP")
@@ -456,17 +451,21 @@ class EP(Inference):
         post.alpha = alpha.reshape(n, 1)
         post.sW = sW.reshape(n, 1)
         post.L = DeviceFactor(fh, n, dev, _lib.current_slot())
-        post.L.dense = True                          # predict hands the cross-covariance block in (GP._latent)
+        if dense:
+            post.L.dense = True                      # predict hands the cross-covariance block in (GP._latent)
         if nargout > 2:
             dnlZ = dnlZStruct(meanfunc, covfunc, likfunc)
-            gh = np.zeros(1)
-            dnlZ.cov = []
-            for h in range(nc):                                                   # one derivative matrix at a time
-                dK = _lib.f64(covfunc.getDerMatrix(x=x, mode="train", der=h))
-                _lib.check(lib.pgp_dense_grad_term(ctx, _lib.ptr(dK), n, 0.0, _lib.ptr(gh)), "pgp_dense_grad_term")
-                dnlZ.cov.append(np.float64(gh[0]))
             dnlZ.mean = [np.float64(v) for v in g[:nm]]
-            dnlZ.lik = []
+            if dense:
+                gh = np.zeros(1)
+                dnlZ.cov = []
+                for h in range(len(hyp)):                                         # one derivative matrix at a time
+                    dK = _lib.f64(covfunc.getDerMatrix(x=x, mode="train", der=h))
+                    _lib.check(lib.pgp_dense_grad_term(ctx, _lib.ptr(dK), n, 0.0, _lib.ptr(gh)), "pgp_dense_grad_term")
+                    dnlZ.cov.append(np.float64(gh[0]))
+            else:
+                dnlZ.cov = [np.float64(v) for v in g[nm:nm + nc]]
+            dnlZ.lik = [np.float64(g[nm + nc])] if nlik else []
             return post, np.float64(nlZ[0]), dnlZ
         return post, np.float64(nlZ[0])
 
@@ -643,14 +642,18 @@ class FITC_Exact(Inference):
 
 
 class FITC_EP(Inference):
-    """FITC-EP approximation to the posterior GP (Core/inf.py:810-944): EP with lik.Erf on Kt = Q + diag(K - Q),
-    Q = Ku' inv(Kuu + snu2 I) Ku, snu2 = 1e-6 (Erf has no noise hyper-parameter, inf.py:837-841).  One device call
-    (csrc/fitc.hip, pgp_fitc_ep_fit): 128-site block sweeps in O(n nu) memory.  ``last_ttau`` / ``last_tnu`` persist across
+    """FITC-EP approximation to the posterior GP (Core/inf.py:810-944): EP with lik.Erf or lik.Laplace on Kt = Q + diag(K - Q),
+    Q = Ku' inv(Kuu + snu2 I) Ku, snu2 = 1e-6 for Erf (no noise hyper-parameter) and 1e-6 sn2 for Laplace (inf.py:837-841).
+    One device call (csrc/fitc.hip, pgp_fitc_ep_fit_lik): 128-site block sweeps in O(n nu) memory.  ``last_ttau`` / ``last_tnu`` persist across
     calls and warm-start the next one as the reference's do (inf.py:857-870); ones of another length start cold.
     ``sweeps``: EP sweeps of the last call.
 
     One deviation: at 10 sweeps this logs the warning "maximum number of sweeps reached" as inf.EP does, where the reference
-    raises AttributeError (FITC_EP.__init__ never sets self.logger, inf.py:823-826)."""
+    raises AttributeError (FITC_EP.__init__ never sets self.logger, inf.py:823-826).
+
+    With lik.Laplace, dnlZ.lik = -sum dlZhyp + snu2 (covariance-like term) (inf.py:925-936).  The reference evaluates dlZhyp at
+    nu_n / tau_n + m, but _epfitcZ's nu_n already carries m tau_n, so a non-zero mean counts twice; the default is the cavity
+    nu_n / tau_n (central differences agree), ``reference_compat = True`` reproduces the reference's point."""
 
     def __init__(self):
         self.name = 'FITC Expectation Propagation'
@@ -658,12 +661,19 @@ class FITC_EP(Inference):
         self.last_tnu = None
         self.device = None
         self.sweeps = 0
+        self.reference_compat = False
+        self._tol_exp = None            # private: sweep tolerance 10^-_tol_exp instead of the reference's 1e-4 (gradient checks)
 
     def evaluate(self, meanfunc, covfunc, likfunc, x, y, nargout=1):
         if not isinstance(covfunc, _cov.FITCOfKernel):
             raise NotImplementedError("pygps_amd: FITC_EP needs a FITC covariance (covfunc.fitc(u)); only covFITC is supported")
-        if not isinstance(likfunc, _lik.Erf):
-            raise NotImplementedError("pygps_amd: FITC_EP runs on the device for lik.Erf only (no CPU fallback)")
+        if isinstance(likfunc, _lik.Laplace):
+            lik, likhyp = _lib.LIK_LAPLACE, _lib.f64(np.asarray(likfunc.hyp, dtype=float).reshape(-1))
+        elif isinstance(likfunc, _lik.Erf):
+            lik, likhyp = _lib.LIK_ERF, None
+        else:
+            raise NotImplementedError("pygps_amd: FITC_EP runs on the device for lik.Erf and lik.Laplace only (no CPU fallback)")
+        nlik = 0 if likhyp is None else 1
         dev = _lib.default_device() if self.device is None else self.device
         kind, para, flags = _device_kernel(covfunc.covfunc, _lib.ctx(dev))
         x = _lib.f64(x)
@@ -684,14 +694,24 @@ class FITC_EP(Inference):
         alpha = np.empty(nu)
         Lm = np.empty((nu, nu))
         nlZ = np.zeros(1)
-        g = np.zeros(nm + nc)
+        g = np.zeros(nm + nc + nlik)
         sweeps = C.c_int()
         fh = C.c_void_p()
-        rc = _lib.load().pgp_fitc_ep_fit(_lib.ctx(dev), kind, _lib.ptr(hyp), nc, int(para), int(flags), _lib.ptr(xu), nu,
-                                         _lib.ptr(m), _lib.ptr(dm), nm, int(min(max(nargout, 1), 3)), int(warm),
-                                         _lib.ptr(ttau), _lib.ptr(tnu), _lib.ptr(alpha), _lib.ptr(Lm), _lib.ptr(nlZ),
-                                         _lib.ptr(g), C.byref(sweeps), C.byref(fh))
-        _lib.check(rc, "pgp_fitc_ep_fit")
+        lib, ctx = _lib.load(), _lib.ctx(dev)
+        if self._tol_exp is not None:
+            _lib.check(lib.pgp_set_option(ctx, b"ep_tol_exp", int(self._tol_exp)), "pgp_set_option")
+            _lib.check(lib.pgp_set_option(ctx, b"ep_max_sweep", 1000), "pgp_set_option")
+        try:
+            rc = lib.pgp_fitc_ep_fit_lik(ctx, kind, _lib.ptr(hyp), nc, int(para), int(flags), lik,
+                                         _lib.ptr(likhyp) if nlik else None, nlik, int(bool(self.reference_compat)),
+                                         _lib.ptr(xu), nu, _lib.ptr(m), _lib.ptr(dm), nm, int(min(max(nargout, 1), 3)),
+                                         int(warm), _lib.ptr(ttau), _lib.ptr(tnu), _lib.ptr(alpha), _lib.ptr(Lm),
+                                         _lib.ptr(nlZ), _lib.ptr(g), C.byref(sweeps), C.byref(fh))
+        finally:
+            if self._tol_exp is not None:
+                lib.pgp_set_option(ctx, b"ep_tol_exp", 4)
+                lib.pgp_set_option(ctx, b"ep_max_sweep", 10)
+        _lib.check(rc, "pgp_fitc_ep_fit_lik")
         self.sweeps = sweeps.value
         if self.sweeps == 10:
             logging.getLogger(__name__).warning("maximum number of sweeps reached in function infEP")
@@ -708,7 +728,7 @@ class FITC_EP(Inference):
                 dnlZ = dnlZStruct(meanfunc, covfunc, likfunc)
                 dnlZ.mean = [np.float64(v) for v in g[:nm]]
                 dnlZ.cov = [np.float64(v) for v in g[nm:nm + nc]]
-                dnlZ.lik = []
+                dnlZ.lik = [np.float64(v) for v in g[nm + nc:]]
                 return post, nlz, dnlZ
             return post, nlz
         return post
