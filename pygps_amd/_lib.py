@@ -122,6 +122,7 @@ TEST_SIGNATURES = {
     "pgp_test_wave_costs": (C.c_int, [_vp, _dp]),
     "pgp_test_stream_concurrency": (C.c_int, [_vp, C.c_int, _dp]),
     "pgp_test_slot_probe": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]),
+    "pgp_test_hadamard": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, _dp]),
 }
 
 _lock = threading.RLock()

@@ -769,3 +769,48 @@ extern "C" int pgp_test_laplace_ep_lik(pgp_ctx* c, const double* y, const double
     HIP_TRY(hipMemcpy(out, od, (size_t)4 * n * 8, hipMemcpyDeviceToHost));
     return PGP_OK;
 }
+
+// self-test hook: the fits' gradient pass (hadamard_reduce_launch) alone, on host Binv / alpha over the resident data of
+// pgp_set_data.  Binv (n x n, symmetric, row-major) goes into an np x np buffer laid out as the fit leaves it (Binv[r * np + c],
+// read for c >= r); the padding and the lower triangle hold NaN, as pooled scratch may hold any bit pattern.  x is scaled into
+// XsT as the fit does, and make_spec / gram_assembly_applies decide the ARD form and the Gram prep exactly as for a fit.
+// wv == nullptr: the exact fit's weights 1 / sn2; else Q_rc = Binv_rc wv_r wv_c - alpha_r alpha_c.  out: ncov sums, sn2 tr(Q).
+extern "C" int pgp_test_hadamard(pgp_ctx* c, int kind, const double* hyp, int ncov, int para, int flags, const double* Binv,
+                                 const double* alpha, const double* wv, double sn2, double* out) {
+    if (!c) return -1;
+    GateShared device_gate_hold(c);
+    if (c->n <= 0) return -1;
+    if (!hyp || !Binv || !alpha || !out) return -2;
+    HIP_TRY(hipSetDevice(c->device));
+    const long n = c->n, d = c->d, np = c->np;
+    CovSpec cp;
+    CHK(make_spec(c, kind, hyp, ncov, para, flags, -1, d, cp));
+    if (cp.ncov != ncov) return -11;
+    hipStream_t st = c->st;
+    const double nan = std::nan("");
+    std::vector<double> hB((size_t)np * np, nan), ha(np, nan), hw(np, nan);
+    for (long r = 0; r < n; ++r)
+        for (long q = r; q < n; ++q) hB[(size_t)r * np + q] = Binv[(size_t)r * n + q];
+    for (long r = 0; r < n; ++r) { ha[r] = alpha[r]; if (wv) hw[r] = wv[r]; }
+    PoolScratch tmp(c);
+    double *XsT = nullptr, *scd = nullptr, *Bd = nullptr, *ad = nullptr, *wd = nullptr, *partial = nullptr, *prep = nullptr,
+           *od = nullptr;
+    CHK(tmp.alloc(&XsT, (size_t)c->dpad * np * sizeof(double)));
+    CHK(tmp.alloc(&scd, (size_t)c->dpad * sizeof(double)));
+    CHK(tmp.alloc(&Bd, (size_t)np * np * sizeof(double)));
+    CHK(tmp.alloc(&ad, (size_t)np * sizeof(double)));
+    if (wv) CHK(tmp.alloc(&wd, (size_t)np * sizeof(double)));
+    CHK(tmp.alloc(&partial, (size_t)hadamard_partial_count(np, ncov) * sizeof(double)));
+    CHK(tmp.alloc(&prep, (size_t)hadamard_prep_count(np) * sizeof(double)));
+    CHK(tmp.alloc(&od, (size_t)(ncov + 1) * sizeof(double)));
+    HIP_TRY(hipMemcpyAsync(Bd, hB.data(), hB.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ad, ha.data(), np * sizeof(double), hipMemcpyHostToDevice, st));
+    if (wv) HIP_TRY(hipMemcpyAsync(wd, hw.data(), np * sizeof(double), hipMemcpyHostToDevice, st));
+    CHK(upload_scaled(c, c->x_dev, n, d, cp.scale, XsT, np, c->dpad, scd));
+    const bool gram = gram_assembly_applies(c, cp);
+    if (gram) CHK(hadamard_prepare_launch(XsT, np, n, np, c->dpad, cp, prep, st, /*force=*/true));
+    CHK(hadamard_reduce_launch(XsT, np, n, np, c->dpad, cp, ncov, sn2, Bd, np, ad, partial, od, st, wd, gram ? prep : nullptr));
+    HIP_TRY(hipMemcpyAsync(out, od, (size_t)(ncov + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return PGP_OK;
+}
