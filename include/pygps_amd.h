@@ -1,6 +1,8 @@
 /* pygps_amd -- C ABI of the MI355X-native exact-GP core (drop-in for the hot path of
  * marionmari/pyGPs: Core/cov.py kernel-matrix construction + Core/inf.py Exact/EP inference +
- * Core/tools.py jitchol/solve_chol + Core/gp.py predict).
+ * Core/tools.py jitchol/solve_chol + Core/gp.py predict).  Covariance functions: the stationary kernels that are functions of
+ * one squared distance, Sum / Product / Scale trees over them, and the spectral mixture kernel PGP_COV_SM, which has tile code
+ * and a fused gradient pass of its own and travels through the same entry points.
  *
  * Plain C, caller-owned host buffers, fp64, numpy row-major unless stated.  No exception crosses
  * the ABI.  Every function returns an int status:
@@ -40,7 +42,12 @@ typedef struct pgp_fitc pgp_fitc;     /* FITC posterior on the device (alpha, de
 #define PGP_COV_PERIODIC 8 /* Core/cov.py:1186-1250 hyp=[log ell, log p, log sf], 1-d inputs only    */
 #define PGP_COV_NOISE 9   /* Core/cov.py:1254-1300 hyp=[log sf]                                      */
 #define PGP_COV_CONST 10  /* Core/cov.py:941-982   hyp=[log sf]  (sf2 = exp(hyp0), as the reference) */
-#define PGP_COV_NKIND 11
+#define PGP_COV_SM 11     /* Core/cov.py:454-619   spectral mixture, para=Q, hyp=[log w (Q) | log m (D x Q) | log sqrt(v) (D x Q)],
+                           * nhyp = Q (1 + 2 D) <= 255 and D <= 16 (else -13).  The product over the coordinates as documented
+                           * (GPML covSM); the reference agrees for D = 1 and sums partial products for D > 1.  Own tile code:
+                           * not a leaf of a composite program (pgp_set_composite stores any tokens; the pgp_cov / fit call that
+                           * expands a program with such a leaf answers -2) */
+#define PGP_COV_NKIND 12
 /* Sum / Product / Scale tree over primitives (Core/cov.py:230-328; up to two ARD leaves), registered with
  * pgp_set_composite and selected by kind = PGP_COV_COMPOSITE in pgp_cov / pgp_exact_fit / pgp_ep_fit.
  * hyp is the composite's flattened list in the reference's order (cov1.hyp + cov2.hyp; [scalar] + cov.hyp). */

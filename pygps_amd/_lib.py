@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PYGPS_AMD_LIB") or os.path.join(_HERE, "libpygps_amd.so")
 
 COV_RBF, COV_RBFARD, COV_MATERN, COV_RBFUNIT, COV_RQ, COV_PIECEPOLY = 0, 1, 2, 3, 4, 5
-COV_RQARD, COV_GABOR, COV_PERIODIC, COV_NOISE, COV_CONST = 6, 7, 8, 9, 10
+COV_RQARD, COV_GABOR, COV_PERIODIC, COV_NOISE, COV_CONST, COV_SM = 6, 7, 8, 9, 10, 11
 COV_COMPOSITE = 100
 PROG_LEAF, PROG_SUM, PROG_PRODUCT, PROG_SCALE = 1, 2, 3, 4
 PROG_MAX_ARD_DIM = 64             # input dimensions of the (single) ARD leaf of a device program

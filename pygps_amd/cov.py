@@ -92,6 +92,7 @@ class Kernel(object):
 
     _WRONG_DER = "Wrong derivative index"
     _BAD_PARA = "invalid kernel parameter"
+    _OVER_LIMIT = "the covariance function exceeds the limits of the device code; there is no CPU fallback"
 
     def _device_eval(self, x, z, mode, der):
         if mode not in _MODES:
@@ -113,7 +114,7 @@ class Kernel(object):
         rc = _lib.load().pgp_cov(_lib.ctx(), kind, _MODES[mode], -1 if der is None else int(der), _lib.ptr(xa), n,
                                  _lib.ptr(za), m, d, _lib.ptr(hyp), len(hyp), int(para), int(flags), _lib.ptr(out))
         _lib.check(rc, "pgp_cov", {-4: self._WRONG_DER, -11: "number of hyperparameters does not match the input dimension",
-                                   -12: self._BAD_PARA})
+                                   -12: self._BAD_PARA, -13: self._OVER_LIMIT})
         return out
 
 
@@ -310,6 +311,96 @@ class Const(_DeviceKernel):
     def __init__(self, log_sigma=0.):
         self.hyp = [log_sigma]
         self.para = []
+
+
+class SM(Kernel):
+    """Gaussian spectral mixture kernel (Wilson & Adams 2013; Core/cov.py:454-619):
+
+        k(x, z) = sum_q w_q prod_j exp(-2 pi^2 v_jq t_j^2) cos(2 pi m_jq t_j),   t_j = x_j - z_j
+
+    hyp = [log w (Q) | log m (D x Q, row-major) | log sqrt(v) (D x Q, row-major)], para = [Q].  For D = 1 this is what the
+    reference computes; for D > 1 it is the documented product over the coordinates (GPML's covSM) with the hyper layout of
+    the reference's ``getCovMatrix`` for the value and the derivatives alike -- the reference itself sums partial products
+    there and decodes ``der`` against a transposed layout (deviations).  The derivative w.r.t. log m_jq is taken in
+    the leave-one-out form w E prod_{j' != j} c_j' (-a sin a) instead of the reference's -a tan(a) K: the same away from the
+    poles of tan, finite at them.
+
+    Evaluated by tile code of its own on the device (csrc/sqdist_tile.h sm_elem, csrc/grad.hip hadamard_sm_kernel) for
+    D <= 16 and Q (1 + 2 D) <= 255; beyond that every call raises.  Not a leaf of a device program: trees that contain it
+    (``SM + Noise``, ``SM * RBF``) combine the children's device-built matrices and fit through the dense route."""
+    _kind = _lib.COV_SM
+    _WRONG_DER = "Wrong derivative entry in SM"
+    _BAD_PARA = "SM needs Q >= 1 mixture components"
+    _OVER_LIMIT = "pygps_amd: cov.SM runs on the device for D <= 16 and Q (1 + 2 D) <= 255; there is no CPU fallback"
+    MAX_D = 16                   # csrc/sqdist_tile.h SM_MAXD: one staged slab of coordinates per tile
+    MAX_HYP = 255                # the library's cap on covariance hypers (SM_MAXHYP)
+
+    def __init__(self, Q=0, hyps=[], D=None):
+        if D:
+            self.hyp = list(np.random.random(Q * (1 + 2 * D)))
+        else:
+            self.hyp = hyps
+        self.para = [Q]
+
+    def initSMhypers(self, x, y):
+        """Initialise the hypers as the reference documents it (Core/cov.py:488-519; the reference's own body raises TypeError
+        on every call): weights std(y) / Q; per coordinate, means uniform in (0, Nyquist frequency] with Nyquist = 0.5 / (smallest
+        non-zero shift), and sqrt(v) = 1 / (largest shift * uniform).  Draws from ``np.random`` in the reference's order
+        (per coordinate: ``ranf(Q)`` for the means, then ``ranf(Q)`` for the scales).  Host only."""
+        x = np.atleast_2d(np.asarray(x, dtype=float))
+        y = np.atleast_2d(np.asarray(y, dtype=float))
+        n, D = x.shape
+        Q = self.para[0]
+        w = np.std(y) / Q
+        m = np.ones((D, Q))
+        s = np.ones((D, Q))
+        for i in range(D):
+            shift = np.abs(x[:, i][:, None] - x[:, i][None, :])
+            nz = shift[shift > 0]
+            minshift = max(nz.min() if nz.size else 1.0, 1e-6)
+            maxshift = max(nz.max() if nz.size else 1.0, 1e-6)
+            m[i, :] = 0.5 / minshift * np.random.ranf(Q)
+            s[i, :] = 1. / np.abs(maxshift * np.random.ranf(Q))
+        self.hyp = [float(np.log(w))] * Q + [float(v) for v in np.log(m.ravel())] + [float(v) for v in np.log(s.ravel())]
+
+    def _check_limits(self, D=None):
+        Q = int(self.para[0])
+        nh = len(self.hyp)
+        if D is None and Q > 0:
+            D = (nh // Q - 1) // 2
+        if D is not None and D > self.MAX_D:
+            raise Exception("pygps_amd: cov.SM runs on the device for input dimension D <= %d (got D = %d); there is no CPU "
+                            "fallback" % (self.MAX_D, D))
+        if nh > self.MAX_HYP or (D is not None and Q * (1 + 2 * D) > self.MAX_HYP):
+            raise Exception("pygps_amd: cov.SM runs on the device for Q (1 + 2 D) <= %d hyperparameters (got %d); there is no "
+                            "CPU fallback" % (self.MAX_HYP, max(nh, Q * (1 + 2 * (D or 0)))))
+
+    def _device_params(self):
+        self._check_limits()
+        return self._kind, int(self.para[0]), 0
+
+    def _program(self, h0):
+        return None                                       # own tile code, not a functor of one squared distance
+
+    def _dim(self, x, z, mode):
+        ref = z if mode == 'self_test' else x
+        if ref is None:
+            return                                        # _device_eval raises the reference's message
+        D = np.shape(ref)[1]
+        assert self.para[0] == len(self.hyp) / (1 + 2 * D)        # Core/cov.py:528 (true division: a ragged hyp fails here)
+        self._check_limits(D)
+
+    def getCovMatrix(self, x=None, z=None, mode=None):
+        self.checkInputGetCovMatrix(x, z, mode)
+        self._dim(x, z, mode)
+        return self._device_eval(x, z, mode, None)
+
+    def getDerMatrix(self, x=None, z=None, mode=None, der=None):
+        self.checkInputGetDerMatrix(x, z, mode, der)
+        self._dim(x, z, mode)
+        if der < 0 or der >= len(self.hyp):
+            raise Exception(self._WRONG_DER)
+        return self._device_eval(x, z, mode, der)
 
 
 # ---- composites (Core/cov.py:230-328) ---------------------------------------------------------------------

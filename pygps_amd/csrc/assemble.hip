@@ -102,6 +102,8 @@ __device__ __forceinline__ double prog_elem(const CovParams& p, double s, double
 
 template <class COV> struct is_program { static constexpr bool value = false; };
 template <> struct is_program<CovProgram> { static constexpr bool value = true; };
+template <class COV> struct is_sm { static constexpr bool value = false; };
+template <> struct is_sm<CovSM> { static constexpr bool value = true; };
 
 // first-slab share of one thread: 2 double2 of the row slab, 2 of the column slab (same split as sqdist_tile)
 struct SlabRegs { double2_t r[2], c[2]; };
@@ -209,7 +211,8 @@ __device__ __forceinline__ void slab_accum(const double* __restrict__ smx, doubl
 }
 
 // COV = CovParams (one functor, the hot path) or CovProgram (Sum/Product/Scale tree; elements are evaluated in a
-// rolled loop over LDS-staged distances so that the eight leaf functors are instantiated once, not 16 times).
+// rolled loop over LDS-staged distances so that the eight leaf functors are instantiated once, not 16 times) or CovSM (spectral
+// mixture: no distance tile; every element is evaluated from the staged coordinates themselves, in a rolled loop as well).
 //
 // Persistent workgroups, software-pipelined over tiles: the coordinates of tile i+1 are fetched into registers
 // BEFORE the stores of tile i are issued (vmcnt retires in order on gfx9, so a load queued behind 32 KB of stores
@@ -233,6 +236,7 @@ __global__ __launch_bounds__(256) void cov_tile_kernel(const double* __restrict_
                                                        long ldo, const int2* __restrict__ tiles, long ntiles, int nt) {
     constexpr int TS = ST + 2;                      // transpose-tile row stride (16-byte aligned rows)
     constexpr bool PROG = is_program<COV>::value;
+    constexpr bool SMK = is_sm<COV>::value;         // D <= SKC: the one staged slab holds every coordinate of the tile
     constexpr bool PARD = PROG && KIND >= 1;        // program with an ARD leaf: second (weighted) distance
     constexpr bool PARD2 = PROG && KIND == 2;       // two ARD leaves: a third distance, kept in registers
     constexpr int SMT = PARD ? 2 * 16 * 256 : (MODE == MODE_SYM ? ST * TS : (PROG ? 16 * 256 : 2));
@@ -264,9 +268,15 @@ __global__ __launch_bounds__(256) void cov_tile_kernel(const double* __restrict_
         for (int a = 0; a < 4; ++a)
 #pragma unroll
             for (int b = 0; b < 4; ++b) { s[a][b] = 0.0; if (PARD) s1[a][b] = 0.0; if (PARD2) s2[a][b] = 0.0; }
-        if constexpr (PARD2) slab_accum3(smx, s, s1, s2, prog_ardw(cp), prog_ardw2(cp), 0);
+        if constexpr (SMK) {
+#pragma unroll 1
+            for (int e = 0; e < 16; ++e) {
+                const int rl = 4 * tr + (e >> 2), cl = 2 * tc + (e & 1) + 32 * ((e >> 1) & 1);
+                put16(s, e, sm_elem(cp, smx + rl, smx + SKC * ST + cl));
+            }
+        } else if constexpr (PARD2) slab_accum3(smx, s, s1, s2, prog_ardw(cp), prog_ardw2(cp), 0);
         else if constexpr (PARD) slab_accum2(smx, s, s1, prog_ardw(cp), 0); else slab_accum(smx, s);
-        for (int k0 = SKC; k0 < dpad; k0 += SKC) {          // d > 16: further slabs, loaded in place
+        for (int k0 = SKC; !SMK && k0 < dpad; k0 += SKC) {  // d > 16: further slabs, loaded in place
             SlabRegs h;
             slab_fetch(XrT, ldr, r0, XcT, ldc, c0, k0, h);
             __syncthreads();
@@ -277,7 +287,7 @@ __global__ __launch_bounds__(256) void cov_tile_kernel(const double* __restrict_
         }
 
         double v[4][4];
-        if (PROG) {
+        if constexpr (PROG) {
             __syncthreads();                            // slabs consumed; the staging area overlays them
             double* sv = sm + t;
             double* sv1 = sm + 16 * 256 + t;
@@ -301,7 +311,7 @@ __global__ __launch_bounds__(256) void cov_tile_kernel(const double* __restrict_
 #pragma unroll
             for (int e = 0; e < 16; ++e) s[e >> 2][e & 3] = sv[e * 256];
         }
-        if (!PROG) tile_values_sel<MODE, KIND, DER>(cp, s, v, XrT, ldr, XcT, ldc, r0, c0, n, inv_sn2);
+        if constexpr (!PROG && !SMK) tile_values_sel<MODE, KIND, DER>(cp, s, v, XrT, ldr, XcT, ldc, r0, c0, n, inv_sn2);
         else {
 #pragma unroll
             for (int a = 0; a < 4; ++a)
@@ -864,7 +874,11 @@ static int cov_tile_dispatch(const CovSpec& cs, int train, long ntr, long ntc_, 
     if (ntiles == 0) return PGP_OK;
     const unsigned nblk = cs.asm_grid > 0 ? (unsigned)std::min<long>(ntiles, cs.asm_grid) : (unsigned)ntiles;
     const int nt_ = cs.asm_nt >= 0 ? cs.asm_nt : ((MODE != MODE_FACTOR && (double)n * (double)m * 8.0 >= 1073741824.0) ? 1 : 0);
-    if (cs.prog) {
+    if (cs.sm) {
+        const CovSM P = sm_resolved(cs);
+        hipLaunchKernelGGL((cov_tile_kernel<MODE, CovSM, 0, false, false>), dim3(nblk), dim3(256), 0, st, XrT, ldr, n, XcT, ldc, m,
+                           dpad, P, inv_sn2, out, ldo, tiles, ntiles, nt_);
+    } else if (cs.prog) {
         CovProgram pg = cs.pg;
         for (int l = 0; l < pg.nleaf; ++l) pg.leaf[l].train = train;
         for (int la : {pg.ard_leaf, pg.ard_leaf2})
@@ -968,7 +982,7 @@ static int cov_gram_dispatch(int mode, const double* XT, long ldp, long n, long 
 }
 bool cov_gram_applies(const CovSpec& cs, int dpad) {
     // dpad <= HADAMARD_PREP_MU: the prep buffer holds that many coordinate means in front of the norms (plain RBF has no cap on d)
-    return !cs.prog && (cs.cp.kind == 0 || cs.cp.kind == 1) && cs.cp.der < 0 && dpad >= 32 && dpad <= HADAMARD_PREP_MU;
+    return !cs.prog && !cs.sm && (cs.cp.kind == 0 || cs.cp.kind == 1) && cs.cp.der < 0 && dpad >= 32 && dpad <= HADAMARD_PREP_MU;
 }
 int cov_factor_gram_launch(const double* XT, long ldp, long n, long np, int dpad, const CovSpec& cs, double inv_sn2, double* Bf,
                            long ldf, const double* prep, hipStream_t st) {
@@ -1002,6 +1016,10 @@ __global__ void cov_self_kernel(COV cp, int same, double* out) {
 
 // train = 1: a diagonal entry of the training matrix; train = 2: 'self_test'
 int cov_self_launch(const CovSpec& cs, int train, double* out_dev, hipStream_t st) {
+    if (cs.sm) {                                      // t = 0: sum_q w_q; d / d log w_q = w_q, every other derivative 0
+        const CovSM P = sm_resolved(cs);
+        return self_fill_launch(out_dev, 1, P.dt < 0 ? cs.cp.sf2 : (P.dt == 0 ? P.h[P.dq] : 0.0), st);
+    }
     if (cs.prog) {
         CovProgram pg = cs.pg;
         for (int l = 0; l < pg.nleaf; ++l) pg.leaf[l].train = train;

@@ -349,6 +349,29 @@ int make_spec(pgp_ctx* c, int kind, const double* hyp, int nhyp, int para, int f
     cs = CovSpec{};
     if (c) { cs.asm_grid = c->asm_grid; cs.asm_nt = c->asm_nt; cs.gram_fast = c->gram_fast; cs.gram_grid = c->gram_grid; }
     if (!hyp && nhyp > 0) return -10;
+    if (kind == PGP_COV_SM) {
+        // spectral mixture: a description of its own (sqdist_tile.h CovSM), unscaled coordinates.  Before the one-leaf-program
+        // branch below, which would otherwise take every kind from PGP_COV_GABOR up
+        const long Q = para;
+        if (Q < 1) return -12;
+        if (d > SM_MAXD || Q * (1 + 2 * d) > SM_MAXHYP) return -13;
+        if ((long)nhyp != Q * (1 + 2 * d)) return -11;
+        if (der >= nhyp) return -4;
+        CovSM& P = cs.smp;
+        P = CovSM{};
+        P.Q = (int)Q; P.D = (int)d; P.dt = -1; P.dj = -1; P.dq = 0;
+        const long double pi = 3.14159265358979323846264338327950288L;
+        long double sw = 0.0L;
+        for (long q = 0; q < Q; ++q) { P.h[q] = (double)expl((long double)hyp[q]); sw += expl((long double)hyp[q]); }
+        for (long i = 0; i < d * Q; ++i) {                                        // each rounded once
+            P.h[Q + i] = (double)(2.0L * pi * expl((long double)hyp[Q + i]));
+            P.h[Q + d * Q + i] = (double)(2.0L * pi * pi * expl(2.0L * (long double)hyp[Q + d * Q + i]));
+        }
+        cs.sm = true; cs.scale.assign(d, 1.0); cs.ncov = nhyp; cs.nder = nhyp;
+        cs.cp = CovParams{};
+        cs.cp.kind = kind; cs.cp.der = der; cs.cp.D = (int)d; cs.cp.train = 1; cs.cp.sf2 = (double)sw;   // k(x,x) = sum_q w_q
+        return PGP_OK;
+    }
     if (kind >= PGP_COV_GABOR && kind < PGP_COV_NKIND) {
         // trigonometric / index-dependent primitives run as one-leaf programs (see sqdist_tile.h cov_value<EXT>)
         CovProgram& P = cs.pg;

@@ -718,6 +718,134 @@ __global__ __launch_bounds__(256) void hadamard_prog_kernel(const double* __rest
     if (t == 0) out[ncov] = tt;
 }
 
+// The gradient pass of the spectral mixture kernel: ONE sweep over the tiles of Q produces all Q_sm (1 + 2 D) sums.  A thread
+// cannot hold that many accumulators for its 16 entries, so the components are finished one at a time: for component q the
+// 1 + 2 D sums over the thread's entries live in registers, are reduced across the wave and parked in LDS (one row per wave, no
+// barrier inside the loop); the four rows meet once at the end.  Entries and coordinates run in rolled loops (one copy of the
+// sin / cos / exp code); what the second pass over the coordinates needs of the first -- c_j = cos a_j and a_j sin a_j of the
+// current entry -- is parked per thread in LDS, so the leave-one-out products prod_{j' != j} c_j' cost D multiplications each.
+// The entries' weights Q_rc wait in LDS too: a register array read at a run-time entry index ends up in scratch memory.
+// Dynamic LDS: 2 D 64 (coordinate slabs) + 2 D 256 (per-thread c_j, a_j sin a_j) + 16 x 256 (weights) + 4 (ncov + 1) (per-wave
+// sums) doubles: 37 KB at D = 1, 118 KB at D = 16.
+__global__ __launch_bounds__(256) void hadamard_sm_kernel(const double* __restrict__ XT, long ldp, long n, CovSM P, int ncov,
+                                                          double inv_sn2, double sn2, const double* __restrict__ Binv, long ldb,
+                                                          const double* __restrict__ alpha, const double* __restrict__ wv,
+                                                          double* __restrict__ partial, long nt, long b0) {
+    extern __shared__ __attribute__((aligned(16))) double smd[];
+    const int D = P.D, NQ = P.Q, nacc = ncov + 1;
+    const int t = threadIdx.x, tr = t >> 4, tc = t & 15, lane = t & 63, wave = t >> 6;
+    double* xr = smd;
+    double* xc = smd + D * ST;
+    double* cj = smd + 2 * D * ST;
+    double* aj = cj + D * 256;
+    double* wl = aj + D * 256 + t;                    // entry e of this thread at wl[e * 256]
+    double* red = aj + D * 256 + 16 * 256;
+    const double* M = P.h + NQ;
+    const double* V = M + NQ * D;
+    const long b = blockIdx.x + b0;
+    long r = (long)(((2.0 * nt + 1.0) - sqrt((2.0 * nt + 1.0) * (2.0 * nt + 1.0) - 8.0 * (double)b)) * 0.5);
+    if (r < 0) r = 0;
+    while (r > 0 && r * nt - r * (r - 1) / 2 > b) --r;
+    while ((r + 1) * nt - (r + 1) * r / 2 <= b) ++r;
+    const long ti = r, tj = ti + (b - (r * nt - r * (r - 1) / 2));
+    const long r0 = ti * ST, c0 = tj * ST;
+    for (int v = t; v < D * 32; v += 256) {           // D coordinates x 32 double2 per point set
+        const int k = v >> 5, pr = v & 31;
+        *(double2_t*)(xr + k * ST + 2 * pr) = *(const double2_t*)(XT + (long)k * ldp + r0 + 2 * pr);
+        *(double2_t*)(xc + k * ST + 2 * pr) = *(const double2_t*)(XT + (long)k * ldp + c0 + 2 * pr);
+    }
+    // weight * Q_rc, Q_rc = Binv_rc * w_r w_c - alpha_r alpha_c (as hadamard_reduce_kernel)
+    double tq = 0.0;
+    double ar[4], ac[4], wr[4], wc[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const long rr = r0 + 4 * tr + a;
+        ar[a] = rr < n ? alpha[rr] : 0.0;
+        wr[a] = wv ? (rr < n ? wv[rr] : 0.0) : inv_sn2;
+    }
+#pragma unroll
+    for (int bq = 0; bq < 4; ++bq) {
+        const long cc = c0 + 2 * tc + (bq & 1) + 32 * (bq >> 1);
+        ac[bq] = cc < n ? alpha[cc] : 0.0;
+        wc[bq] = wv ? (cc < n ? wv[cc] : 0.0) : 1.0;
+    }
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const long rr = r0 + 4 * tr + a;
+#pragma unroll
+        for (int bh = 0; bh < 2; ++bh) {
+            const long cb = c0 + 2 * tc + 32 * bh;
+            const double2_t bv = *(const double2_t*)(Binv + rr * ldb + cb);
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int bq = 2 * bh + e;
+                const long cc = cb + e;
+                double wt = (cc > rr) ? 2.0 : (cc == rr ? 1.0 : 0.0);     // symmetric: count the mirror
+                if (rr >= n || cc >= n) wt = 0.0;                          // padding
+                const double q = bv[e] * (wr[a] * wc[bq]) - ar[a] * ac[bq];
+                wl[(4 * a + bq) * 256] = (wt != 0.0) ? wt * q : 0.0;       // never let unused entries in
+                if (cc == rr && rr < n) tq += sn2 * q;
+            }
+        }
+    }
+    __syncthreads();
+    double* rw = red + wave * nacc;
+#pragma unroll 1
+    for (int q = 0; q < NQ; ++q) {
+        double gw = 0.0, gm[SM_MAXD], gv[SM_MAXD];
+#pragma unroll
+        for (int j = 0; j < SM_MAXD; ++j) gm[j] = gv[j] = 0.0;
+        const double wq = P.h[q];
+#pragma unroll 1
+        for (int e = 0; e < 16; ++e) {
+            const double we = wl[e * 256];
+            if (we == 0.0) continue;
+            const double* pr_ = xr + 4 * tr + (e >> 2);
+            const double* pc_ = xc + 2 * tc + (e & 1) + 32 * ((e >> 1) & 1);
+            double ex = 0.0, pc = 1.0;
+#pragma unroll 1
+            for (int j = 0; j < D; ++j) {
+                const double tt = pr_[j * ST] - pc_[j * ST];
+                const double a = M[j * NQ + q] * tt;
+                double sa, ca;
+                sincos(a, &sa, &ca);
+                cj[j * 256 + t] = ca;
+                aj[j * 256 + t] = a * sa;
+                ex = fma(V[j * NQ + q] * tt, tt, ex);
+                pc *= ca;
+            }
+            const double base = we * wq * exp_nonpos(-ex);                 // Q_rc w_q E_q
+            const double Cq = base * pc;
+            gw += Cq;
+#pragma unroll
+            for (int j = 0; j < SM_MAXD; ++j) {
+                if (j < D) {
+                    double loo = base;
+#pragma unroll 1
+                    for (int j2 = 0; j2 < D; ++j2) loo *= (j2 == j) ? 1.0 : cj[j2 * 256 + t];
+                    gm[j] = fma(loo, -aj[j * 256 + t], gm[j]);
+                    const double tt = pr_[j * ST] - pc_[j * ST];
+                    gv[j] = fma(Cq, -2.0 * V[j * NQ + q] * tt * tt, gv[j]);
+                }
+            }
+        }
+        gw = wave_sum(gw);
+        if (lane == 0) rw[q] = gw;
+#pragma unroll
+        for (int j = 0; j < SM_MAXD; ++j) {
+            if (j < D) {
+                const double sm_ = wave_sum(gm[j]), sv_ = wave_sum(gv[j]);
+                if (lane == 0) { rw[NQ + j * NQ + q] = sm_; rw[NQ + NQ * D + j * NQ + q] = sv_; }
+            }
+        }
+    }
+    tq = wave_sum(tq);
+    if (lane == 0) rw[ncov] = tq;
+    __syncthreads();
+    double* out = partial + (long)blockIdx.x * (long)nacc;
+    for (int h = t; h < nacc; h += 256) out[h] = (red[h] + red[nacc + h]) + (red[2 * nacc + h] + red[3 * nacc + h]);
+}
+
 // out[h] = sum_b partial[b*nacc + h], fixed order; one block per h
 __global__ __launch_bounds__(256) void final_reduce_kernel(const double* __restrict__ partial, long nblk, int nacc,
                                                            double* __restrict__ out) {
@@ -936,7 +1064,7 @@ long hadamard_block_count(long np, long tr0, long trn) {
 long hadamard_prep_count(long np) { return HADAMARD_PREP_MU + np; }
 int hadamard_prepare_launch(const double* XT, long ldp, long n, long np, int dpad, const CovSpec& cs, double* mu, hipStream_t st,
                             bool force) {
-    const bool ard = force || (cs.prog ? cs.pg.ard_leaf >= 0 : (cs.cp.kind == 1 || cs.cp.kind == 6));
+    const bool ard = force || (cs.prog ? cs.pg.ard_leaf >= 0 : (!cs.sm && (cs.cp.kind == 1 || cs.cp.kind == 6)));
     if (ard && dpad > HADAMARD_PREP_MU) return PGP_ERR_HIP;            // the mean region of the prep buffer (callers gate on it)
     if (ard) hipLaunchKernelGGL(coord_mean_kernel, dim3((unsigned)dpad), dim3(256), 0, st, XT, ldp, n, mu);
     if (ard && !cs.prog)
@@ -955,7 +1083,15 @@ int hadamard_partial_launch(const double* XT, long ldp, long n, long np, int dpa
     const long b0 = tri_blocks_before(nt, tr0);
     const long nblk = tri_blocks_before(nt, tr0 + trn) - b0;
     if (nblk <= 0) return PGP_OK;
-    if (cs.prog) {
+    if (cs.sm) {
+        CovSM P = cs.smp;
+        P.dt = -1;
+        if (ncov != P.Q * (1 + 2 * P.D) || P.D > dpad) return -11;
+        const size_t shm = ((size_t)2 * P.D * ST + (size_t)2 * P.D * 256 + 16 * 256 + (size_t)4 * (ncov + 1)) * sizeof(double);
+        func_max_dynamic_lds((const void*)hadamard_sm_kernel, shm);
+        hipLaunchKernelGGL(hadamard_sm_kernel, dim3((unsigned)nblk), dim3(256), shm, st, XT, ldp, n, P, ncov, 1.0 / sn2, sn2, Binv,
+                           ldb, alpha, wv, partial, nt, b0);
+    } else if (cs.prog) {
         CovProgram pg = cs.pg;
         for (int l = 0; l < pg.nleaf; ++l) pg.leaf[l].train = 1;
         if (cs.ard_grad_diff) mu = nullptr;           // the kernels' switch to the difference-form per-coordinate sums

@@ -52,6 +52,17 @@ struct CovProgram {
     double ardw2[CP_MAXARD];
 };
 
+// Spectral mixture kernel (Wilson & Adams 2013; Core/cov.py:454-619, GPML covSM with the product over the coordinates):
+//   k(x,z) = sum_q w_q exp(-2 pi^2 sum_j v_jq t_j^2) prod_j cos(2 pi m_jq t_j),   t_j = x_j - z_j.
+// Not a function of one squared distance, so it has tile code of its own (sm_elem below, hadamard_sm_kernel in grad.hip)
+// beside the functor chains.  Coordinates are uploaded unscaled; D <= SKC keeps a tile's coordinates in one slab.
+constexpr int SM_MAXHYP = 255, SM_MAXD = 16;
+struct CovSM {
+    int Q, D;
+    int dt, dj, dq;                  // derivative resolved: dt = -1 value, 0 log w_q, 1 log m_jq, 2 log sqrt(v_jq)
+    double h[SM_MAXHYP + 1];         // the hyper layout of the reference: [w_q | 2 pi m_jq | 2 pi^2 v_jq], (j, q) at j * Q + q
+};
+
 constexpr int ST = 64;      // tile edge
 constexpr int SKC = 16;     // coordinates staged per step
 
@@ -481,11 +492,50 @@ __device__ __forceinline__ void cov_deriv_all(const CovParams& p, double s, doub
     }
 }
 
+// One entry of the spectral mixture value or derivative matrix.  xr / xc: the row / column point inside the LDS slabs
+// (coordinate j at [j * ST]).  One exp per component on the accumulated exponent, one cosine per component and coordinate.
+// Derivatives (log space) of component q = P.dq, C = w E prod_j c_j:  log w: C;  log m_j: w E prod_{j' != j} c_j' (-a sin a),
+// a = 2 pi m_j t_j (the leave-one-out form of the reference's -a tan(a) C: no 0 * inf at the poles);  log sqrt(v_j):
+// C (-(2 pi)^2 v_j t_j^2).  Everything is even in t_j: the signed difference serves.
+__device__ __forceinline__ double sm_elem(const CovSM& P, const double* __restrict__ xr, const double* __restrict__ xc) {
+    const double* M = P.h + P.Q;
+    const double* V = M + P.Q * P.D;
+    if (P.dt < 0) {
+        double K = 0.0;
+#pragma unroll 1
+        for (int q = 0; q < P.Q; ++q) {
+            double ex = 0.0, pr = P.h[q];
+#pragma unroll 1
+            for (int j = 0; j < P.D; ++j) {
+                const double t = xr[j * ST] - xc[j * ST];
+                ex = fma(V[j * P.Q + q] * t, t, ex);
+                pr *= cos(M[j * P.Q + q] * t);
+            }
+            K = fma(pr, exp_nonpos(-ex), K);
+        }
+        return K;
+    }
+    const int q = P.dq;
+    double ex = 0.0, pr = P.h[q];
+#pragma unroll 1
+    for (int j = 0; j < P.D; ++j) {
+        const double t = xr[j * ST] - xc[j * ST];
+        const double a = M[j * P.Q + q] * t, u = V[j * P.Q + q] * t * t;
+        ex += u;
+        double f = cos(a);
+        if (j == P.dj) f = P.dt == 1 ? -a * sin(a) : (P.dt == 2 ? -2.0 * u * f : f);
+        pr *= f;
+    }
+    return pr * exp_nonpos(-ex);
+}
+
 // host-side description of the covariance function of one call: a primitive functor or a program
 struct CovSpec {
     bool prog = false;
     CovParams cp;
     CovProgram pg;
+    bool sm = false;                // spectral mixture: `smp` describes it, cp.der holds the flat derivative index, cp.sf2 = sum_q w_q
+    CovSM smp;
     std::vector<double> scale;      // per-coordinate scale folded into XsT (all ones for programs)
     int ncov = 0;                   // number of hyperparameters (= gradient entries)
     int nder = 0;                   // getDerMatrix accepts der in [0, nder)
@@ -499,6 +549,17 @@ struct CovSpec {
     int gram_grid = 32768;          // Gram-form assembly: persistent workgroups per launch (option "gram_grid")
     double sf2() const { return cp.sf2; }
 };
+
+// the spectral mixture description of a spec with its derivative index (cp.der, hyp layout of CovSM::h) resolved
+inline CovSM sm_resolved(const CovSpec& cs) {
+    CovSM P = cs.smp;
+    const int der = cs.cp.der, QD = P.Q * P.D;
+    P.dt = der < 0 ? -1 : (der < P.Q ? 0 : (der < P.Q + QD ? 1 : 2));
+    const int r = der < P.Q ? 0 : (der - P.Q) % (QD > 0 ? QD : 1);
+    P.dq = der < 0 ? 0 : (der < P.Q ? der : r % P.Q);
+    P.dj = (der < P.Q) ? -1 : r / P.Q;
+    return P;
+}
 
 // ---- composite programs ----------------------------------------------------------------------------
 __device__ __forceinline__ bool cov_is_ard(const CovParams& p) { return p.kind == 1 || p.kind == 6; }
