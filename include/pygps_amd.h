@@ -180,6 +180,23 @@ int pgp_laplace_fit_dense(pgp_ctx* ctx, const double* K, int lik, const double* 
                           const double* dm, int nmean, int want, int warm, double* alpha_io, double* sW_out, double* nlZ_out,
                           double* dnlZ_out, int* steps_out, double* trace_out, pgp_factor** factor_out);
 
+/* ---- GPMC.fitAndPredict (Core/gp.py:829-863): one-vs-one multi-class classification on ONE shared covariance matrix -------------
+ * Every pair (i, j), i < j, of the n_class classes is a binary GPC with lik.Erf on the rows of the two classes (class i first,
+ * labelled +1, then class j, -1, each in data order: createBinaryClass, gp.py:905-928), and all pairs share mean, kernel and
+ * hyper-parameters.  K_all = k(x_all, x_all) and, per batch of test points, Ks_all = k(x_all, xs) are assembled once on the
+ * device; every pair's fit (cold start, want = 2) and predict work on gathered principal submatrices / row subsets, and the votes
+ * (gp.py:854-862) are accumulated and normalised on the device.  x_all: the x of the last pgp_set_data (its y is not used).
+ * kind / covhyp / ncov / para / flags as pgp_ep_fit_lik.  inference: 0 = EP, 1 = Laplace.  labels (n): integer class of every
+ * row, each class in [0, n_class) with at least one row (-8 otherwise).  m_all (n) / ms (ns): the prior mean at x_all / xs (NULL:
+ * zero).  xs (ns, d).  votes_out (ns, n_class) row-major, rows sum to 1.  pair_nlZ_out / pair_iters_out (n_class (n_class - 1) / 2,
+ * optional): nlZ and EP sweeps / Newton steps per pair in the order (0,1), (0,2), ..., (n_class-2, n_class-1).  Returns > 0: the
+ * first bad pivot of the pair written to bad_pair_out (2 ints, optional), which also names the pair of any other failure;
+ * -1 .. -99 bad argument; <= -100 HIP failure.  pgp_last_timings afterwards: assemble = K_all + Ks_all, solve = the fits,
+ * potrf = the pairs' predicts, grad = the vote kernels, total = the whole call (ms). */
+int pgp_gpmc_fit_predict(pgp_ctx* ctx, int kind, const double* covhyp, int ncov, int para, int flags, int inference,
+                         const int32_t* labels, int n_class, const double* m_all, const double* xs, int64_t ns, const double* ms,
+                         double* votes_out, double* pair_nlZ_out, int32_t* pair_iters_out, int32_t* bad_pair_out);
+
 /* ---- FITC sparse regression: FITC_Exact.evaluate (Core/inf.py:398-455) with FITCOfKernel (Core/cov.py:332-390)
  * x, y of the last pgp_set_data; xu (nu,d) inducing inputs.  alpha_out (nu), L_out (nu,nu) = post.L (dense,
  * symmetric; NULL to skip), dnlZ_out = [mean.., cov.., lik].  snu2 = 1e-6 sn2 like the reference (inf.py:410).

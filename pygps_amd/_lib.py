@@ -64,6 +64,8 @@ SIGNATURES = {
                                   C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.POINTER(C.c_int), _dp, C.POINTER(_vp)]),
     "pgp_laplace_fit_dense": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp,
                                         _dp, _dp, C.POINTER(C.c_int), _dp, C.POINTER(_vp)]),
+    "pgp_gpmc_fit_predict": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, _dp, _dp,
+                                       _i64, _dp, _dp, _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "pgp_fitc_fit": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _i64, _dp, _dp, C.c_int,
                                C.c_int, _dp, _dp, _dp, _dp, C.POINTER(_vp)]),
     "pgp_fitc_predict": (C.c_int, [_vp, _vp, _dp, _i64, _dp, _dp, _dp]),
@@ -123,6 +125,8 @@ TEST_SIGNATURES = {
     "pgp_test_stream_concurrency": (C.c_int, [_vp, C.c_int, _dp]),
     "pgp_test_slot_probe": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]),
     "pgp_test_hadamard": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, _dp]),
+    "pgp_test_gather_sym": (C.c_int, [_vp, _dp, _i64, C.POINTER(C.c_int32), _i64, _i64, _dp, _dp, _dp, _dp]),
+    "pgp_test_vote": (C.c_int, [_vp, _dp, _dp, _i64, C.c_int, C.c_int, C.c_int, _dp, _dp]),
 }
 
 _lock = threading.RLock()

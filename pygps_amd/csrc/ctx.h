@@ -448,3 +448,26 @@ int solve_lower_multi(pgp_ctx* c, const double* L, long ldl, const double* Wd, d
                       bool trans);
 int potrf_blocked_rhs(pgp_ctx* c, double* F, long ld, long np, long mrows, double* R, long ldr, long nrhs2);
 int eet_lower(pgp_ctx* c, const double* E, long lde, double* Binv, long ldb, long np);
+
+// ---- GPMC (gpmc.hip): one-vs-one pairs on one shared covariance matrix ----------------------------------------------------
+// The third source of the training covariance of the dense EP / Laplace drivers, beside "device program" and "dense upload":
+// a principal submatrix of a matrix that is already on the device.  The drivers gather it straight into the padded buffer
+// they factor from (gather_sym_launch) and take the labels and the prior mean from the same launch instead of c->y_dev / mvec.
+struct GatherSrc {
+    long n = 0;                        // points of this fit (c->n is the size of the resident x_all)
+    long n_pos = 0;                    // the first n_pos rows are labelled +1, the others -1 (GPMC.createBinaryClass)
+    const double* K_all = nullptr;     // (device) full symmetric, column-major, leading dimension ld
+    long ld = 0;
+    const int* idx = nullptr;          // (device) n rows of K_all: two ascending runs, not globally sorted
+    const double* m_all = nullptr;     // (device) the prior mean at every row of K_all
+    double* y = nullptr;               // (device, np) written by the gather: the pair's labels ...
+    double* m = nullptr;               // (device, np) ... and its prior mean
+};
+// Kd (np x np, np = round_up(g.n, 128)): Kd[r, c] = K_all[idx[r], idx[c]] on the live part, zeros on the padding; g.y and g.m
+int gather_sym_launch(const GatherSrc& g, double* Kd, long np, hipStream_t st);
+// cold-start fits (want = 2, no gradients) on the gathered submatrix; the posterior handle is the dense drivers' (no coordinates)
+int ep_fit_gathered(pgp_ctx* c, const GatherSrc& g, double* nlZ_out, int* sweeps_out, pgp_factor** factor_out);
+int laplace_fit_gathered(pgp_ctx* c, const GatherSrc& g, double* nlZ_out, int* steps_out, pgp_factor** factor_out);
+// the device core of pgp_predict_dense on a block that is already on the device: Ks (f->np x nrhs, one column per test point,
+// zero padding; overwritten), msd (nb) prior mean; o1 = fmu, o2 = colsum((R'^-1 (sW o Ks))^2)  (fs2 = max(kss - o2, 0))
+int predict_dense_block(pgp_ctx* c, pgp_factor* f, double* Ks, long nb, int nrhs, const double* msd, double* o1, double* o2);

@@ -974,6 +974,7 @@ struct EpWork {
     unsigned chain_total, prep_total, strip_total;   // their values once everything launched so far has run (strips in launches)
     int lik;                             // PGP_LIK_ERF or PGP_LIK_LAPLACE
     double sn;                           // lik.Laplace: exp(hyp[0])
+    const double* y_d;                   // the labels: c->y_dev, or the gathered pair's (GatherSrc)
 };
 
 }  // namespace
@@ -1065,7 +1066,7 @@ static int ep_compute_params(pgp_ctx* c, EpWork& w, const std::vector<double>& y
     CHK(logdet_ztz_launch(w.F, w.ldf, n, w.F, 0, c->scal, st));
     const long nblk_terms = (n + 255) / 256;
     std::vector<double> part_h(5 * nblk_terms);
-    hipLaunchKernelGGL(ep_site_terms_kernel, dim3((unsigned)nblk_terms), dim3(256), 0, st, n, c->y_dev, w.m_d, w.mu_d, w.diag_d, 0.0,
+    hipLaunchKernelGGL(ep_site_terms_kernel, dim3((unsigned)nblk_terms), dim3(256), 0, st, n, w.y_d, w.m_d, w.mu_d, w.diag_d, 0.0,
                        w.ttau_d, w.tnu_d, 1, w.tmp_d, (double*)nullptr, w.lik, w.sn, (double*)nullptr);
     HIP_TRY(hipMemcpyAsync(part_h.data(), w.tmp_d, part_h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     double sc[2];
@@ -1137,6 +1138,8 @@ extern "C" int pgp_test_probit_hazard(pgp_ctx* c, const double* z, double* out, 
 // dnlZ_out.  Kdense != nullptr (pgp_ep_fit_dense): K (n x n, symmetric, host) is handed in -- a covariance tree that is not
 // a device program --; dnlZ_out receives the mean gradients only, and R = sW sW' o B^-1 and alpha stay in the context's
 // workspace for the pgp_dense_grad_term calls that follow (1/2 sum (R - alpha alpha') o dK_h, inf.py:780-786).
+// gk != nullptr (ep_fit_gathered): K is a principal submatrix of a matrix that is already on the device; it is gathered straight into
+// the padded buffer, with the labels and the prior mean of its rows (n, np and ldf are the submatrix's, not the resident data's).
 // a bounded device-side wait of the block sweep gave up: say which one (site 1 prep<-chain, 2 prep<-strip, 3 chain<-prep, 4 bulk<-chain)
 static int ep_wait_failed(const unsigned* eflags, unsigned chain_total, unsigned prep_total, unsigned strip_total, int line) {
     char msg[256];
@@ -1150,17 +1153,20 @@ static int ep_wait_failed(const unsigned* eflags, unsigned chain_total, unsigned
 static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double* covhyp, int ncov, int para, int flags,
                        const double* mvec, const double* dm, int nmean, int want, int warm, double* ttau_io, double* tnu_io,
                        double* alpha_out, double* sW_out, double* nlZ_out, double* dnlZ_out, int* sweeps_out,
-                       pgp_factor** factor_out, int lik = PGP_LIK_ERF, double sn = 0.0, int ref_compat = 0) {
+                       pgp_factor** factor_out, int lik = PGP_LIK_ERF, double sn = 0.0, int ref_compat = 0,
+                       const GatherSrc* gk = nullptr) {
     if (!c) return -1;
-    if (c->n <= 0) return -1;
-    if (!covhyp && !Kdense) return -3;
+    if (gk ? gk->n <= 0 : c->n <= 0) return -1;
+    if (!covhyp && !Kdense && !gk) return -3;
     if (!ttau_io || !tnu_io) return -12;
     GateShared gate(c);                              // shared for the fit, exclusive during each block sweep (ctx.h DeviceGate)
     HIP_TRY(hipSetDevice(c->device));
     c->dense_ready = false;                          // the workspace (B^-1, alpha) is about to be rewritten
     hipStream_t st = c->st;
-    const long n = c->n, d = c->d, np = c->np, ldf = c->ldf;
-    const bool dense = Kdense != nullptr;
+    // K: a device program over the resident x, a dense upload, or (gk) a principal submatrix gathered on the device (gpmc.hip)
+    const long n = gk ? gk->n : c->n, d = c->d, np = gk ? round_up(n, 128) : c->np, ldf = gk ? np + 128 : c->ldf;
+    const bool dense = Kdense != nullptr || gk != nullptr;
+    const double* const y_dev = gk ? gk->y : c->y_dev;
     CovSpec cp;
     if (dense) ncov = 0;
     else { const int rc = make_spec(c, kind, covhyp, ncov, para, flags, -1, d, cp); if (rc != PGP_OK) return rc == -11 ? -10 : rc; }
@@ -1193,7 +1199,7 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
     };
     EpWork w{};
     w.n = n; w.np = np; w.ldf = ldf;
-    w.lik = lik; w.sn = sn;
+    w.lik = lik; w.sn = sn; w.y_d = y_dev;
     const size_t nn = (size_t)np * np * sizeof(double);
     // RAII: every early return (HIP_TRY / EP_TRY / CHK) gives the scratch back to the context's pool, scrubs + returns the
     // factor buffer and frees a half-built handle -- no hipMalloc / hipFree (device-synchronising) on the steady-state path
@@ -1224,7 +1230,8 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
     FactorGuard fguard(c, w.F, (size_t)ldf * np * sizeof(double), /*scrub=*/true);
     stamp("scratch acquired");
     // ---- K (full symmetric, padded with zeros) --------------------------------------------------------
-    if (dense) HIP_TRY(hipMemcpy2DAsync(w.Kd, np * sizeof(double), Kdense, n * sizeof(double), n * sizeof(double), n, hipMemcpyHostToDevice, st));
+    if (gk) EP_TRY(gather_sym_launch(*gk, w.Kd, np, st));                               // already on the device, gathered
+    else if (dense) HIP_TRY(hipMemcpy2DAsync(w.Kd, np * sizeof(double), Kdense, n * sizeof(double), n * sizeof(double), n, hipMemcpyHostToDevice, st));
     else {
         EP_TRY(upload_scaled(c, c->x_dev, n, d, sc, c->XsT, np, c->dpad, c->scale_dev));
         if (gram_assembly_applies(c, cp)) {            // RBF / RBFard at d >= 32 (cfg 5: d = 32): the Gram form on the matrix cores
@@ -1235,8 +1242,9 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
     }
     std::vector<double> m(n, 0.0), y(n), ttau(n, 0.0), tnu(n, 0.0), mu(n, 0.0), dsig(n, kdiag);
     if (mvec) memcpy(m.data(), mvec, n * sizeof(double));
-    HIP_TRY(hipMemcpyAsync(y.data(), c->y_dev, n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(w.m_d, m.data(), n * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(y.data(), y_dev, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (gk) HIP_TRY(hipMemcpyAsync(w.m_d, gk->m, n * sizeof(double), hipMemcpyDeviceToDevice, st));     // gathered with K
+    else HIP_TRY(hipMemcpyAsync(w.m_d, m.data(), n * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
     // nlZ0 = -sum lik(y, m, diag K)  (inf.py:737)
     double nlZ0 = 0.0;
@@ -1244,7 +1252,7 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
         const long nbt = (n + 255) / 256;
         std::vector<double> ph(5 * nbt);
         if (dense) EP_TRY(gather_strided_launch(w.Kd, np + 1, np, w.diag_d, st));          // K_ii differs from point to point
-        hipLaunchKernelGGL(ep_site_terms_kernel, dim3((unsigned)nbt), dim3(256), 0, st, n, c->y_dev, w.m_d, (const double*)nullptr,
+        hipLaunchKernelGGL(ep_site_terms_kernel, dim3((unsigned)nbt), dim3(256), 0, st, n, y_dev, w.m_d, (const double*)nullptr,
                            dense ? (const double*)w.diag_d : (const double*)nullptr, kdiag, (const double*)nullptr, (const double*)nullptr,
                            1, w.tmp_d, (double*)nullptr, lik, sn, (double*)nullptr);
         HIP_TRY(hipMemcpyAsync(ph.data(), w.tmp_d, ph.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1325,7 +1333,7 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
                 auto kern = lik == PGP_LIK_LAPLACE ? (ep_timing ? ep_chain_kernel<true, PGP_LIK_LAPLACE> : ep_chain_kernel<false, PGP_LIK_LAPLACE>)
                                                    : (ep_timing ? ep_chain_kernel<true, PGP_LIK_ERF> : ep_chain_kernel<false, PGP_LIK_ERF>);
                 hipLaunchKernelGGL(kern, dim3(37), dim3(512), EP_BLOCK_LDS, sa, w.Sig, np, n, (int)nbl, w.mu_d, w.m_d,
-                                   c->y_dev, w.ttau_d, w.tnu_d, w.Wb, w.gb, w.ldb, yfl, ep_timing ? (long long*)(w.gb + 2 * EPB) : (long long*)nullptr,
+                                   y_dev, w.ttau_d, w.tnu_d, w.Wb, w.gb, w.ldb, yfl, ep_timing ? (long long*)(w.gb + 2 * EPB) : (long long*)nullptr,
                                    w.S, w.tile, w.flags, w.chain_total, w.prep_total, w.strip_total, swg, sn);
             }
             HIP_TRY(hipEventRecord(c->ep_ev[1], sa));
@@ -1410,7 +1418,7 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
         } else
         for (long i = 0; i < n; ++i) {
             hipLaunchKernelGGL(ep_site_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, w.Sig, np, np, i,
-                               w.mu_d, w.m_d, c->y_dev, w.ttau_d, w.tnu_d, w.sbuf, w.coef, lik, sn);
+                               w.mu_d, w.m_d, y_dev, w.ttau_d, w.tnu_d, w.sbuf, w.coef, lik, sn);
             hipLaunchKernelGGL(ep_rank1_mu_kernel, dim3((unsigned)((np + 3) / 4)), dim3(256), 0, st, w.Sig, np, np,
                                w.sbuf, w.coef, w.tnu_d, w.mu_d);
         }
@@ -1430,7 +1438,7 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
             double* const part_d = w.ldb + np / EPB + 3;
             const double* const res_h = c->res_host + (w.ldb - c->res_dev);
             EP_TRY(gather_strided_launch(w.Sig, np + 1, np, w.diag_d, st));
-            hipLaunchKernelGGL(ep_site_terms_kernel, dim3((unsigned)nbt), dim3(256), 0, st, n, c->y_dev, w.m_d, w.mu_d, w.diag_d, 0.0,
+            hipLaunchKernelGGL(ep_site_terms_kernel, dim3((unsigned)nbt), dim3(256), 0, st, n, y_dev, w.m_d, w.mu_d, w.diag_d, 0.0,
                                w.ttau_d, w.tnu_d, 1, part_d, (double*)nullptr, lik, sn, (double*)nullptr);
             if (merge12 && sweep == 1 && 2 * res_slot <= np) {
                 HIP_TRY(hipMemcpyAsync(w.ldb + res_slot, w.ldb, (size_t)res_len * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -1564,7 +1572,7 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
             // (inf.py:796-798).  With it, d lZ_j / d log sn (inf.py:796-798) for dnlZ.lik.
             const int with_m = laplace && !ref_compat ? 1 : 0;
             std::vector<double> dl(n), dh(laplace ? n : 0);
-            hipLaunchKernelGGL(ep_site_terms_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, c->y_dev, w.m_d, w.mu_d,
+            hipLaunchKernelGGL(ep_site_terms_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, y_dev, w.m_d, w.mu_d,
                                w.diag_d, 0.0, w.ttau_d, w.tnu_d, with_m, w.tmp_d, w.sbuf, lik, sn, laplace ? w.coef : (double*)nullptr);
             HIP_TRY(hipMemcpyAsync(dl.data(), w.sbuf, n * sizeof(double), hipMemcpyDeviceToHost, st));
             if (laplace) HIP_TRY(hipMemcpyAsync(dh.data(), w.coef, n * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1610,6 +1618,14 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
     if (dense && want >= 3) { c->dense_ready = true; c->dense_n = n; }
     return PGP_OK;
 #undef EP_TRY
+}
+
+// EP on a principal submatrix of a covariance matrix that is already on the device (gpmc.hip): lik.Erf, cold start, want = 2
+int ep_fit_gathered(pgp_ctx* c, const GatherSrc& g, double* nlZ_out, int* sweeps_out, pgp_factor** factor_out) {
+    if (!g.K_all || !g.idx || !g.y || !g.m || !g.m_all) return -2;
+    std::vector<double> ttau(g.n, 0.0), tnu(g.n, 0.0);
+    return ep_fit_core(c, nullptr, 0, nullptr, 0, 0, 0, nullptr, nullptr, 0, 2, 0, ttau.data(), tnu.data(), nullptr, nullptr, nlZ_out,
+                       nullptr, sweeps_out, factor_out, PGP_LIK_ERF, 0.0, 0, &g);
 }
 
 extern "C" int pgp_ep_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para, int flags, const double* mvec,

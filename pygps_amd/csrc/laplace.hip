@@ -272,9 +272,9 @@ int lap_solve(pgp_ctx* c, LapWork& w, const double* s, const double* v) {
 static int laplace_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double* covhyp, int ncov, int para, int flags,
                             int lik, const double* likhyp, int nlik, const double* mvec, const double* dm, int nmean, int want,
                             int warm, double* alpha_io, double* sW_out, double* nlZ_out, double* dnlZ_out, int* steps_out,
-                            double* trace_out, pgp_factor** factor_out) {
+                            double* trace_out, pgp_factor** factor_out, const GatherSrc* gk = nullptr) {
     if (!c) return -1;
-    if (c->n <= 0) return -1;
+    if (gk ? gk->n <= 0 : c->n <= 0) return -1;
     if (lik != PGP_LIK_ERF && lik != PGP_LIK_GAUSS) return -7;
     if (lik == PGP_LIK_GAUSS && (!likhyp || nlik != 1)) return -8;
     if (lik == PGP_LIK_ERF && nlik != 0) return -9;
@@ -284,8 +284,10 @@ static int laplace_fit_core(pgp_ctx* c, const double* Kdense, int kind, const do
     HIP_TRY(hipSetDevice(c->device));
     c->dense_ready = false;                          // the workspace (B^-1, alpha) is about to be rewritten
     hipStream_t st = c->st;
-    const long n = c->n, d = c->d, np = c->np, ldf = c->ldf;
-    const bool dense = Kdense != nullptr;
+    // K: a device program over the resident x, a dense upload, or (gk) a principal submatrix gathered on the device (gpmc.hip)
+    const long n = gk ? gk->n : c->n, d = c->d, np = gk ? round_up(n, 128) : c->np, ldf = gk ? np + 128 : c->ldf;
+    const bool dense = Kdense != nullptr || gk != nullptr;
+    const double* const y_dev = gk ? gk->y : c->y_dev;
     const double sn2 = lik == PGP_LIK_GAUSS ? exp(2.0 * likhyp[0]) : 1.0;
     CovSpec cp;
     if (dense) ncov = 0;
@@ -333,7 +335,8 @@ static int laplace_fit_core(pgp_ctx* c, const double* Kdense, int kind, const do
     CHK(alloc_factor_buffer(c, np, ldf, &w.F));
     FactorGuard fguard(c, w.F, (size_t)ldf * np * sizeof(double), /*scrub=*/true);
     // ---- K (full symmetric, padded with zeros) --------------------------------------------------------------------
-    if (dense) HIP_TRY(hipMemcpy2DAsync(w.Kd, np * sizeof(double), Kdense, n * sizeof(double), n * sizeof(double), n, hipMemcpyHostToDevice, st));
+    if (gk) CHK(gather_sym_launch(*gk, w.Kd, np, st));                                  // already on the device, gathered
+    else if (dense) HIP_TRY(hipMemcpy2DAsync(w.Kd, np * sizeof(double), Kdense, n * sizeof(double), n * sizeof(double), n, hipMemcpyHostToDevice, st));
     else {
         CHK(upload_scaled(c, c->x_dev, n, d, cp.scale, c->XsT, np, c->dpad, c->scale_dev));
         if (gram_assembly_applies(c, cp)) {
@@ -342,10 +345,11 @@ static int laplace_fit_core(pgp_ctx* c, const double* Kdense, int kind, const do
         } else
             CHK(cov_sym_launch(c->XsT, np, n, c->dpad, cp, w.Kd, st, np));
     }
-    if (mvec) HIP_TRY(hipMemcpyAsync(w.m, mvec, n * sizeof(double), hipMemcpyHostToDevice, st));
+    if (gk) HIP_TRY(hipMemcpyAsync(w.m, gk->m, n * sizeof(double), hipMemcpyDeviceToDevice, st));       // gathered with K
+    else if (mvec) HIP_TRY(hipMemcpyAsync(w.m, mvec, n * sizeof(double), hipMemcpyHostToDevice, st));
     double red[4];
     auto eval = [&](const double* alpha_or_null, bool with_d3) -> int {
-        hipLaunchKernelGGL(lap_eval_kernel, dim3(1), dim3(LAP_LS), 0, st, n, np, lik, sn2, c->y_dev, w.f, w.m, alpha_or_null,
+        hipLaunchKernelGGL(lap_eval_kernel, dim3(1), dim3(LAP_LS), 0, st, n, np, lik, sn2, y_dev, w.f, w.m, alpha_or_null,
                            w.lp, w.dlp, w.W, with_d3 ? w.d3lp : nullptr, w.res);
         HIP_TRY(hipMemcpyAsync(red, w.res, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -362,7 +366,7 @@ static int laplace_fit_core(pgp_ctx* c, const double* Kdense, int kind, const do
         // the reference's "objective for default init f == m" (inf.py:486-487) is the first element of -lp(y, m): vargout[0] of
         // the negated vector, not its sum.  Restated as it is, so that a warm call takes the branches the reference takes.
         double lp0, d1, d2, y0;
-        HIP_TRY(hipMemcpy(&y0, c->y_dev, sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&y0, y_dev, sizeof(double), hipMemcpyDeviceToHost));
         const double m0 = mvec ? mvec[0] : 0.0;
         if (lik == PGP_LIK_GAUSS) gauss_laplace_derivs(y0, m0, sn2, &lp0, &d1, &d2, nullptr);
         else erf_laplace_derivs(y0, m0, &lp0, &d1, &d2, nullptr);
@@ -393,10 +397,10 @@ static int laplace_fit_core(pgp_ctx* c, const double* Kdense, int kind, const do
         CHK(lap_solve(c, w, w.sW, w.tmp));                                              // B^-1 (sW o K b)
         hipLaunchKernelGGL(lap_axpy_kernel, lap_grid1(np), dim3(256), 0, st, np, w.b, w.sW, w.rhs, w.alpha, w.da);
         CHK(col_dot_full_launch(w.Kd, np, np, np, w.da, nullptr, w.kda, st));           // K dalpha, once per step
-        hipLaunchKernelGGL(lap_line_kernel, dim3(1), dim3(LAP_LS), 0, st, n, np, lik, sn2, c->y_dev, w.m, w.alpha, w.f, w.da,
+        hipLaunchKernelGGL(lap_line_kernel, dim3(1), dim3(LAP_LS), 0, st, n, np, lik, sn2, y_dev, w.m, w.alpha, w.f, w.da,
                            w.kda, w.dlp, w.W, smax, nline, thr, w.res);
         // the W < 0 test of the next step (inf.py:512) rides in the same read-back
-        hipLaunchKernelGGL(lap_eval_kernel, dim3(1), dim3(LAP_LS), 0, st, n, np, lik, sn2, c->y_dev, w.f, w.m,
+        hipLaunchKernelGGL(lap_eval_kernel, dim3(1), dim3(LAP_LS), 0, st, n, np, lik, sn2, y_dev, w.f, w.m,
                            (const double*)nullptr, w.lp, w.dlp, w.W, (double*)nullptr, w.res + 4);
         double rec[8];
         HIP_TRY(hipMemcpyAsync(rec, w.res, 8 * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -459,7 +463,7 @@ static int laplace_fit_core(pgp_ctx* c, const double* Kdense, int kind, const do
             HIP_TRY(hipMemcpyAsync(Ku.data(), w.tmp, n * sizeof(double), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(g.data(), w.g, n * sizeof(double), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(f.data(), w.f, n * sizeof(double), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(y.data(), c->y_dev, n * sizeof(double), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(y.data(), y_dev, n * sizeof(double), hipMemcpyDeviceToHost, st));
         }
         HIP_TRY(hipStreamSynchronize(st));
         for (int i = 0; i < nmean; ++i) {                                               // -(alpha + u)' dm_i
@@ -507,6 +511,14 @@ static int laplace_fit_core(pgp_ctx* c, const double* Kdense, int kind, const do
     }
     if (dense && want >= 3) { c->dense_ready = true; c->dense_n = n; }
     return PGP_OK;
+}
+
+// Laplace on a principal submatrix of a covariance matrix that is already on the device (gpmc.hip): lik.Erf, cold start, want = 2
+int laplace_fit_gathered(pgp_ctx* c, const GatherSrc& g, double* nlZ_out, int* steps_out, pgp_factor** factor_out) {
+    if (!g.K_all || !g.idx || !g.y || !g.m || !g.m_all) return -2;
+    std::vector<double> alpha(g.n, 0.0);
+    return laplace_fit_core(c, nullptr, 0, nullptr, 0, 0, 0, PGP_LIK_ERF, nullptr, 0, nullptr, nullptr, 0, 2, 0, alpha.data(), nullptr,
+                            nlZ_out, nullptr, steps_out, nullptr, factor_out, &g);
 }
 
 extern "C" int pgp_laplace_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para, int flags, int lik,

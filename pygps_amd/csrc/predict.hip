@@ -200,6 +200,20 @@ static int pred_stage(pgp_ctx* c, size_t doubles) {
     return PGP_OK;
 }
 
+// The device core of pgp_predict_dense (also the per-pair predict of gpmc.hip): Ks (np x nrhs, one column per test point) is
+// already on the device and is overwritten; o1 = fmu, o2 = the raw column sums of squares.
+int predict_dense_block(pgp_ctx* c, pgp_factor* f, double* Ks, long nb_, int nrhs, const double* msd, double* o1, double* o2) {
+    hipStream_t st = c->st;
+    const long np = f->np, n = f->n;
+    CHK(ensure_wd(c, f));
+    CHK(col_dot_full_launch(Ks, np, n, nb_, f->alpha, msd, o1, st));                      // fmu = ms + Ks' alpha
+    if (f->sWv) CHK(row_scale_launch(Ks, np, n, nrhs, f->sWv, st));
+    CHK(solve_lower_multi(c, f->F, f->ldf, f->Wd, Ks, np, np, nrhs, false));
+    // the raw column sums of squares (kss differs per test point here): out = max(BIG - scale * s, 0) would clip, so take
+    // them through kss = 0 with a NEGATIVE scale: out = max(scale' * s, 0) = scale' * s
+    return col_sumsq_launch(Ks, np, n, nb_, 0.0, -(f->sWv ? 1.0 : f->sw * f->sw), o2, st);
+}
+
 extern "C" {
 
 int pgp_predict(pgp_ctx* c, pgp_factor* f, const double* xs, int64_t ns, const double* ms, double* fmu, double* fs2) {
@@ -337,12 +351,7 @@ int pgp_predict_dense(pgp_ctx* c, pgp_factor* f, const double* Ks_host, int64_t 
                                  hipMemcpyHostToDevice, st));
         if (ms) HIP_TRY(hipMemcpyAsync(msd, ms + a, nb_ * sizeof(double), hipMemcpyHostToDevice, st));
         else HIP_TRY(hipMemsetAsync(msd, 0, nb_ * sizeof(double), st));
-        CHK(col_dot_full_launch(Ks, np, n, nb_, f->alpha, msd, o1, st));                  // fmu = ms + Ks' alpha
-        if (f->sWv) CHK(row_scale_launch(Ks, np, n, nrhs, f->sWv, st));
-        CHK(solve_lower_multi(c, f->F, f->ldf, f->Wd, Ks, np, np, nrhs, false));
-        // the raw column sums of squares (kss differs per test point here): out = max(BIG - scale * s, 0) would clip, so take
-        // them through kss = 0 with a NEGATIVE scale: out = max(scale' * s, 0) = scale' * s
-        CHK(col_sumsq_launch(Ks, np, n, nb_, 0.0, -(f->sWv ? 1.0 : f->sw * f->sw), o2, st));
+        CHK(predict_dense_block(c, f, Ks, nb_, nrhs, msd, o1, o2));
         HIP_TRY(hipMemcpyAsync(fmu + a, o1, nb_ * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(fs2 + a, o2, nb_ * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));                          // blk is reused by the next batch

@@ -42,6 +42,15 @@ int pgp_test_hadamard(pgp_ctx* ctx, int kind, const double* hyp, int ncov, int p
                       const double* alpha, const double* wv, double sn2, double* out);
 /* out2[0] = 1 if the context's two streams ran concurrently (a spinner on the panel stream saw a flag set from the main stream), out2[1] = us waited */
 int pgp_test_stream_concurrency(pgp_ctx* ctx, int wait_us, double* out2);
+/* gather_sym_kernel (csrc/gpmc.hip) on a host matrix K (n x n, row-major): Kd_out (np x np, np = n_idx rounded up to 128) with
+   Kd_out[r, c] = K[idx[r], idx[c]] on the live part and zeros on the padding; y_out / m_out (np, optional): +1 for the first n_pos
+   rows, -1 for the other live ones, and m_all[idx[r]] (m_all NULL: zeros) */
+int pgp_test_gather_sym(pgp_ctx* ctx, const double* K, int64_t n, const int32_t* idx, int64_t n_idx, int64_t n_pos,
+                        const double* m_all, double* Kd_out, double* y_out, double* m_out);
+/* vote_accumulate_kernel / vote_normalise_kernel (csrc/gpmc.hip) for ONE pair (ci, cj) at host fmu, fs2 (ns each): votes_out
+   (ns x n_class) before the normalisation, norm_out (optional) after it */
+int pgp_test_vote(pgp_ctx* ctx, const double* fmu, const double* fs2, int64_t ns, int n_class, int ci, int cj, double* votes_out,
+                  double* norm_out);
 #ifdef __cplusplus
 }
 #endif

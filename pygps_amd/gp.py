@@ -1,9 +1,9 @@
-"""Model facade (reference: pyGPs/Core/gp.py -- GP :62-527, GPR :533-635, GPC :641-732).
+"""Model facade (reference: pyGPs/Core/gp.py -- GP :62-527, GPR :533-635, GPC :641-732, GPMC :738-932, FITC :934-1235).
 
 Same public surface for the pieces that call the hot path: ``setData``, ``setPrior``, ``setNoise``,
 ``setOptimizer``, ``optimize``, ``getPosterior``, ``predict``, ``predict_with_posterior`` and the
-result attributes ``nlZ, dnlZ, posterior, ym, ys2, fm, fs2, lp``.  Plotting, FITC and multi-class
-wrappers are out of scope.
+result attributes ``nlZ, dnlZ, posterior, ym, ys2, fm, fs2, lp``; ``GPMC`` is the one-vs-one multi-class wrapper.
+Plotting is out of scope.
 """
 import logging
 from copy import deepcopy
@@ -317,3 +317,240 @@ class GPC_FITC(GP_FITC):
         if newInf == "Laplace":
             raise NotImplementedError("pygps_amd: FITC_Laplace (GPC_FITC.useInference('Laplace')) is not implemented")
         raise Exception('Possible inf values are "Laplace".')
+
+
+class GPMC(object):
+    """One-vs-one multi-class classification (Core/gp.py:738-932): a binary GPC with lik.Erf for each of the
+    n_class (n_class - 1) / 2 pairs of classes, combined by votes.  Zero mean, RBF, EP inference.
+
+    ``fitAndPredict`` / ``optimizeAndPredict`` return the (ns, n_class) matrix of normalised votes.  Two routes produce it
+    (``last_route`` says which one the last call took):
+
+      - "pairs": the reference's loop, a ``GPC`` per pair on the pair's rows (getPosterior or optimize, then predict), votes
+        added on the host.  Always for ``optimizeAndPredict`` (the hyper-parameters differ per pair), for ``fitAndPredict``
+        with ``GPMC(n_class, shared_kernel=False)`` and whenever the shared route cannot run.
+      - "shared" (``fitAndPredict`` only): all pairs share mean, kernel and hyper-parameters, so K(x_all, x_all) and
+        K(x_all, xs) are assembled ONCE on the device and every pair works on a gathered submatrix (pgp_gpmc_fit_predict,
+        csrc/gpmc.hip).  Taken when the kernel is a device functor or device program and the shared matrices fit into
+        ``shared_memory_limit`` bytes (default: the quarter of the device memory that ``DeviceFactor.reserve`` guards).
+
+    ``pair_nlZ`` / ``pair_iters`` (EP sweeps or Newton steps), dicts keyed (i, j), are set by both routes; ``pair_hyp`` (the
+    optimised covariance hyper-parameters per pair) by ``optimizeAndPredict``.
+
+    Deviations from the reference, deliberately:
+      - ``useInference("Laplace")`` takes effect for every pair.  The reference stores ``self.inffunc`` but its loops test
+        ``self.newInf``, which nothing ever sets, so the call is silently ignored there (equivalent to never making it).
+      - a class in range(n_class) without a training point raises a plain Exception naming the class before any device work;
+        the reference goes on and fails later inside a pair."""
+
+    def __init__(self, n_class, shared_kernel=True):
+        self.meanfunc = mean.Zero()                # default prior mean
+        self.covfunc = cov.RBF()                   # default prior covariance
+        self.n_class = n_class                     # number of different classes
+        self.x_all = None
+        self.y_all = None
+        self.newInf = None                         # new inference? -> call useInference
+        self.newLik = None                         # new likelihood? -> call useLikelihood
+        self.newPrior = False
+        self.shared_kernel = bool(shared_kernel)
+        self.shared_memory_limit = None            # bytes the shared route may take; None: a quarter of the device memory
+        self.device = None
+        self.pair_nlZ = {}
+        self.pair_iters = {}
+        self.pair_hyp = {}
+        self.last_route = None
+
+    def setPrior(self, mean=None, kernel=None):
+        from . import mean as _mean
+        if mean is not None:
+            assert isinstance(mean, _mean.Mean), "mean function is not an instance of pygps_amd.mean.Mean"
+            self.meanfunc = mean
+            self.usingDefaultMean = False
+        if kernel is not None:
+            assert isinstance(kernel, cov.Kernel), "cov function is not an instance of pygps_amd.cov.Kernel"
+            self.covfunc = kernel
+        self.newPrior = True
+
+    def useInference(self, newInf):
+        """'Laplace' (Core/gp.py:776-785); unlike the reference's, this call takes effect (class docstring)."""
+        if newInf == "Laplace":
+            self.inffunc = inf.Laplace()
+            self.newInf = "Laplace"
+        else:
+            raise Exception('Possible inf values are "Laplace".')
+
+    def useLikelihood(self, newLik):
+        if newLik == "Logistic":
+            raise Exception("Logistic likelihood is currently not implemented.")
+        else:
+            raise Exception('Possible lik values are "Logistic".')
+
+    def setData(self, x, y):
+        assert x.shape[0] == y.shape[0], "number of inputs and labels does not match"
+        if x.ndim == 1:
+            x = np.reshape(x, (x.shape[0], 1))
+        if y.ndim == 1:
+            y = np.reshape(y, (y.shape[0], 1))
+        self.x_all = x
+        self.y_all = y
+
+    # ---- the pairs ----------------------------------------------------------------------------------------
+    def pairs(self):
+        """The pairs in the order they are processed: (0,1), (0,2), ..., (n_class-2, n_class-1)."""
+        return [(i, j) for i in range(self.n_class) for j in range(i + 1, self.n_class)]
+
+    def _pair_index(self, i, j):
+        t = np.asarray(self.y_all).reshape(-1)
+        ci = np.flatnonzero(t == i)
+        cj = np.flatnonzero(t == j)
+        return np.concatenate([ci, cj]), len(ci)
+
+    def createBinaryClass(self, i, j):
+        """x, y of the rows of class i (in data order, labelled +1) followed by those of class j (-1)  (Core/gp.py:905-928)."""
+        idx, n1 = self._pair_index(i, j)
+        y = np.concatenate((np.ones((1, n1)), -np.ones((1, len(idx) - n1))), axis=1).T
+        return self.x_all[idx, :], y
+
+    def _check_classes(self):
+        t = np.asarray(self.y_all).reshape(-1)
+        for k in range(self.n_class):
+            if not np.any(t == k):
+                raise Exception("GPMC: class %d has no training point" % k)
+
+    def _prior(self):
+        """Mean and kernel every pair's GPC starts with: the user's objects after setPrior, else GPC's defaults."""
+        if self.newPrior:
+            return self.meanfunc, self.covfunc
+        return mean.Zero(), cov.RBF()
+
+    @staticmethod
+    def add_votes(votes, ym, i, j):
+        """gp.py:854-861 for one pair: ym + 1 into column i, 2 - (ym + 1) into column j."""
+        a = np.asarray(ym, dtype=float).reshape(-1) + 1
+        votes[:, i] += a
+        votes[:, j] += 2 - a
+        return votes
+
+    def _new_pair_model(self):
+        model = GPC()
+        if self.newPrior:
+            model.setPrior(mean=self.meanfunc, kernel=self.covfunc)
+        if self.newInf:
+            model.useInference(self.newInf)
+        if self.device is not None:
+            model.inffunc.device = self.device
+        return model
+
+    @staticmethod
+    def _iters(model):
+        return int(model.inffunc.newton_steps if isinstance(model.inffunc, inf.Laplace) else model.inffunc.sweeps)
+
+    def shared_bytes(self, ns):
+        """Device bytes of the shared route: K_all, one batch of Ks_all with the largest pair's block of it, the pairs'
+        factors and the largest pair's fit scratch."""
+        r128 = lambda v: (int(v) + 127) // 128 * 128
+        n = self.x_all.shape[0]
+        np_ = r128(n)
+        t = np.asarray(self.y_all).reshape(-1)
+        cnt = [int(np.sum(t == k)) for k in range(self.n_class)]
+        sizes = [r128(cnt[i] + cnt[j]) for i, j in self.pairs()]
+        nsb = max(128, min(65536, r128(ns), max(16384, (1 << 34) // (8 * np_) // 128 * 128)))      # predict_batch_points
+        big = max(sizes)
+        return 8 * (np_ * np_ + np_ * nsb + big * nsb + sum((s + 128) * s for s in sizes) + 5 * big * big)
+
+    def choose_route(self, ns, device_bytes=None):
+        """"shared" or "pairs" for fitAndPredict on ns test points.  device_bytes: the device's memory (asked of the device
+        only when it is needed and not given)."""
+        if not self.shared_kernel:
+            return "pairs"
+        m, k = self._prior()
+        if isinstance(k, cov._Composite):
+            if not k._on_device():
+                return "pairs"
+        elif not isinstance(k, cov.Kernel) or isinstance(k, cov.FITCOfKernel) or getattr(k, "_kind", None) is None:
+            return "pairs"
+        from . import mean as _mean
+        if not isinstance(m, _mean.Mean):
+            return "pairs"
+        limit = self.shared_memory_limit
+        if limit is None:
+            if device_bytes is None:
+                dev = _lib.default_device() if self.device is None else self.device
+                device_bytes = _lib.device_memory_bytes(dev)
+            limit = 0.25 * device_bytes - inf.DeviceFactor.live_bytes
+        return "shared" if self.shared_bytes(ns) <= limit else "pairs"
+
+    # ---- the two routes -----------------------------------------------------------------------------------
+    def _by_pairs(self, xs, optimize):
+        self.last_route = "pairs"
+        votes = np.zeros((xs.shape[0], self.n_class))
+        for i, j in self.pairs():
+            x, y = self.createBinaryClass(i, j)
+            model = self._new_pair_model()
+            if optimize:
+                model.optimize(x, y)
+                self.pair_hyp[(i, j)] = [float(v) for v in model.covfunc.hyp]
+            else:
+                model.getPosterior(x, y)
+            self.pair_nlZ[(i, j)] = float(model.nlZ)
+            self.pair_iters[(i, j)] = self._iters(model)
+            self.add_votes(votes, model.predict(xs)[0], i, j)
+        votes /= votes.sum(axis=1)[:, np.newaxis]
+        return votes
+
+    def _shared(self, xs):
+        import ctypes as C
+        self.last_route = "shared"
+        dev = _lib.default_device() if self.device is None else self.device
+        ctx = _lib.ctx(dev)
+        meanfunc, covfunc = self._prior()
+        kind, para, flags = covfunc._bind(ctx)
+        x = _lib.f64(self.x_all)
+        n = x.shape[0]
+        xs = _lib.f64(xs)
+        ns = xs.shape[0]
+        if xs.shape[1] != x.shape[1]:
+            raise Exception("GPMC: test inputs have %d columns, training inputs %d" % (xs.shape[1], x.shape[1]))
+        labels = np.ascontiguousarray(np.asarray(self.y_all).reshape(n), dtype=np.int32)
+        inf._Resident.ensure(x, labels.astype(np.float64), dev)
+        m_all = _lib.f64(meanfunc.getMean(x)).reshape(n)
+        ms = _lib.f64(meanfunc.getMean(xs)).reshape(ns)
+        hyp = _lib.f64(np.asarray(covfunc.hyp, dtype=float))
+        pairs = self.pairs()
+        votes = np.empty((ns, self.n_class))
+        nlZ = np.zeros(len(pairs))
+        iters = np.zeros(len(pairs), dtype=np.int32)
+        bad = np.full(2, -1, dtype=np.int32)
+        i32 = C.POINTER(C.c_int32)
+        rc = _lib.load().pgp_gpmc_fit_predict(ctx, kind, _lib.ptr(hyp), len(hyp), int(para), int(flags),
+                                              1 if self.newInf == "Laplace" else 0, labels.ctypes.data_as(i32), int(self.n_class),
+                                              _lib.ptr(m_all), _lib.ptr(xs), ns, _lib.ptr(ms), _lib.ptr(votes), _lib.ptr(nlZ),
+                                              iters.ctypes.data_as(i32), bad.ctypes.data_as(i32))
+        if rc == _lib.ERR_LAPLACE_WNEG:
+            raise NotImplementedError("pygps_amd: Laplace met W < 0 (the reference's LU branch is not restated)")
+        _lib.check(rc, "pgp_gpmc_fit_predict" + (" (pair %d, %d)" % (bad[0], bad[1]) if bad[0] >= 0 else ""))
+        for k, p in enumerate(pairs):
+            self.pair_nlZ[p] = float(nlZ[k])
+            self.pair_iters[p] = int(iters[k])
+        return votes
+
+    def fitAndPredict(self, xs):
+        """Fit every pair at the current hyper-parameters and predict xs (nn, D): the (nn, n_class) matrix of normalised votes,
+        row = test point, column = class  (Core/gp.py:829-863)."""
+        if xs.ndim == 1:
+            xs = np.reshape(xs, (xs.shape[0], 1))
+        self._check_classes()
+        self.pair_nlZ, self.pair_iters, self.pair_hyp = {}, {}, {}
+        if self.choose_route(xs.shape[0]) == "shared":
+            return self._shared(xs)
+        return self._by_pairs(xs, optimize=False)
+
+    def optimizeAndPredict(self, xs):
+        """Optimise every pair's hyper-parameters, then predict xs  (Core/gp.py:867-901).  With a user prior every pair's GPC
+        receives the same kernel and mean objects, so one pair's optimum is the next pair's starting point, as in the
+        reference; without one every pair starts from GPC's defaults."""
+        if xs.ndim == 1:
+            xs = np.reshape(xs, (xs.shape[0], 1))
+        self._check_classes()
+        self.pair_nlZ, self.pair_iters, self.pair_hyp = {}, {}, {}
+        return self._by_pairs(xs, optimize=True)
