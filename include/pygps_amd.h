@@ -47,7 +47,10 @@ typedef struct pgp_fitc pgp_fitc;     /* FITC posterior on the device (alpha, de
                            * (GPML covSM); the reference agrees for D = 1 and sums partial products for D > 1.  Own tile code:
                            * not a leaf of a composite program (pgp_set_composite stores any tokens; the pgp_cov / fit call that
                            * expands a program with such a leaf answers -2) */
-#define PGP_COV_NKIND 12
+#define PGP_COV_PRE 12    /* Core/cov.py:1429-1455 precomputed kernel matrix, no hypers: the value of element (row, col) is read from
+                           * the matrices bound with pgp_set_pre.  Alone or as ONE leaf of a composite program (a second one: -13).
+                           * Fits and pgp_predict only: pgp_cov answers -13 (the Python class slices its host arrays). */
+#define PGP_COV_NKIND 13
 /* Sum / Product / Scale tree over primitives (Core/cov.py:230-328; up to two ARD leaves), registered with
  * pgp_set_composite and selected by kind = PGP_COV_COMPOSITE in pgp_cov / pgp_exact_fit / pgp_ep_fit.
  * hyp is the composite's flattened list in the reference's order (cov1.hyp + cov2.hyp; [scalar] + cov.hyp). */
@@ -87,6 +90,29 @@ int pgp_cov(pgp_ctx* ctx, int kind, int mode, int der, const double* x, int64_t 
  * -- the Python layer then takes the dense path (pgp_exact_fit_dense / pgp_ep_fit_dense).  The PLAIN kinds
  * PGP_COV_RBFARD / PGP_COV_RQARD take any D (the scales are folded into the coordinates). */
 int pgp_set_composite(pgp_ctx* ctx, const int32_t* prog, int nprog);
+
+/* cov.Pre: bind the precomputed matrices of the (one) PGP_COV_PRE leaf to the context; they stay resident until replaced.
+ * M2 (n, n) row-major, symmetric: the training matrix, n = the n of pgp_set_data at fit time (else the fit answers -14).
+ * M1 (n + 1, ns) row-major: cross-covariances with ns test points, last row = their self-covariances; needed by pgp_predict
+ * only (a posterior of a program with this leaf answers -15 when no M1 with ns columns is bound).  Either pointer may be NULL:
+ * that matrix is kept as it is (a new M2 drops the M1 bound before).  -2: M1 without an M2 of this n. */
+int pgp_set_pre(pgp_ctx* ctx, const double* M2, int64_t n, const double* M1, int64_t ns);
+
+/* ---- graph node kernels and the k-NN graph (GraphExtensions/nodeKernels.py, graphUtil.py:29-46) -------------
+ * A (n, n) row-major host: dense symmetric adjacency matrix without isolated nodes; K_out (n, n) row-major host.
+ *   PGP_NODE_REGLAP  inv(I + p0^2 L), L the normalised Laplacian      PGP_NODE_VND   inv(I - p0 S), S = I - L
+ *   PGP_NODE_RW      (p0 I - L)^p1, p1 an integer >= 1                PGP_NODE_DIFF  exp(p0 (A - D))
+ * The inverses are a Cholesky factorisation with its inverse: a matrix that is not positive definite (VND with p0 >= 1)
+ * answers the index of the first bad pivot (> 0) like the fits.  Powers and the exponential (scaled Taylor series of
+ * degree 18 with repeated squaring) are products on the fp64 GEMM. */
+#define PGP_NODE_REGLAP 0
+#define PGP_NODE_VND 1
+#define PGP_NODE_RW 2
+#define PGP_NODE_DIFF 3
+int pgp_node_kernel(pgp_ctx* ctx, int kind, const double* A, int64_t n, double p0, double p1, double* K_out);
+/* pc (n, d) row-major host; A_out (n, n) row-major host: 0 / 1 adjacency of the k-nearest-neighbour graph by brute-force
+ * squared distances, the point itself left out, ties broken by the lower index, symmetrised with max (1 <= k < n). */
+int pgp_knn_graph(pgp_ctx* ctx, const double* pc, int64_t n, int64_t d, int k, double* A_out);
 
 /* ---- data residency -------------------------------------------------------------------------
  * The optimiser calls the fit hundreds of times with identical (x, y) and only hyp changing

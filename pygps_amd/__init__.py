@@ -9,7 +9,7 @@ into it does (no CPU fallback).
 from ._threads import respect_cpu_quota as _respect_cpu_quota
 
 _respect_cpu_quota()            # a container CPU quota below the visible core count: cap the BLAS / OpenMP pools (see _threads.py)
-from . import conf, cov, inf, lik, mean, minimize, opt, tools  # noqa: F401,E402
+from . import GraphExtensions, conf, cov, inf, lik, mean, minimize, opt, tools  # noqa: F401,E402
 from .gp import GP, GPC, GPC_FITC, GPMC, GPR, GP_FITC, GPR_FITC  # noqa: F401,E402
 
 __version__ = "0.1"

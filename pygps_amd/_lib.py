@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("PYGPS_AMD_LIB") or os.path.join(_HERE, "libpygps_amd.
 
 COV_RBF, COV_RBFARD, COV_MATERN, COV_RBFUNIT, COV_RQ, COV_PIECEPOLY = 0, 1, 2, 3, 4, 5
 COV_RQARD, COV_GABOR, COV_PERIODIC, COV_NOISE, COV_CONST, COV_SM = 6, 7, 8, 9, 10, 11
+COV_PRE = 12                      # precomputed matrix (cov.Pre): a resident leaf of the device program, no hypers
 COV_COMPOSITE = 100
 PROG_LEAF, PROG_SUM, PROG_PRODUCT, PROG_SCALE = 1, 2, 3, 4
 PROG_MAX_ARD_DIM = 64             # input dimensions of the (single) ARD leaf of a device program
@@ -42,6 +43,9 @@ SIGNATURES = {
     "pgp_cov": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, _i64, _dp, _i64, _i64, _dp, C.c_int, C.c_int,
                           C.c_int, _dp]),
     "pgp_set_composite": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int]),
+    "pgp_set_pre": (C.c_int, [_vp, _dp, _i64, _dp, _i64]),
+    "pgp_node_kernel": (C.c_int, [_vp, C.c_int, _dp, _i64, C.c_double, C.c_double, _dp]),
+    "pgp_knn_graph": (C.c_int, [_vp, _dp, _i64, _i64, C.c_int, _dp]),
     "pgp_set_data": (C.c_int, [_vp, _dp, _i64, _i64, _dp]),
     "pgp_exact_fit": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _dp, C.c_int,
                                 C.c_int, _dp, _dp, _dp, C.POINTER(_vp)]),

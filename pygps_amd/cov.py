@@ -83,6 +83,13 @@ class Kernel(object):
             return None
         return [_lib.PROG_LEAF, int(kind), int(para), int(flags), int(h0)], 1, 1, ard * 1000
 
+    def _pre_leaves(self):
+        """The cov.Pre leaves of this (sub)tree."""
+        return []
+
+    def _on_device(self):
+        return True
+
     def _bind(self, ctx):
         """Select this kernel on context ``ctx``: returns (kind, para, flags) for the C entry points."""
         if self._kind is None:
@@ -403,6 +410,156 @@ class SM(Kernel):
         return self._device_eval(x, z, mode, der)
 
 
+class Pre(Kernel):
+    """Precomputed kernel matrix (Core/cov.py:1429-1455).  ``M2``: train x train, symmetric.  ``M1``: (train + 1) x test, the
+    cross-covariances with the test points; its last row holds the test points' self-covariances.  ``hyp = []``: nothing is
+    optimised.  Used alone (with a dummy ``x = zeros((n, 1))``) or inside ``+``, ``*`` and ``* number`` trees.
+
+    ``getCovMatrix`` slices the host arrays as the reference does, after checking that ``x`` / ``z`` have as many rows as the
+    matrices (the reference returns all of M1 whatever ``xs`` is and so breaks silently beyond the 1000 test points of one
+    of its predict batches, Core/gp.py:395-406; here predict takes any number of test points, all of them at once).
+
+    Inside fits and predict the matrices are a RESIDENT LEAF of the device program: M2 is uploaded once per context and read
+    by the assembly and gradient tile kernels on every evaluation, M1 once per predict.  Residency is keyed on per-object
+    tokens that change when ``M1`` / ``M2`` are rebound (``k.M2 = ...``); the n^2 doubles are never hashed.  After changing
+    an array IN PLACE call ``touch()``.  ``Pre.device_leaf = False`` (class or instance) sends every tree that holds the
+    kernel down the dense route instead (K and the derivative matrices built on the host per evaluation): the A/B switch.
+
+    One Pre per device program; a tree with two of them fits through the dense route.  FITC, sharded fits and GPMC refuse it."""
+    _kind = _lib.COV_PRE
+    #: False: not a leaf of the device program -- every tree holding this kernel takes the dense route
+    device_leaf = True
+    _token_counter = __import__("itertools").count(1)
+    # context handle -> [token of the M2 it holds, token of the M1 it holds].  Contexts live as long as the process (one per
+    # device and fit stream, _lib.ctx), so the table is never pruned; an entry is read and written only by the thread that
+    # drives that context, under the GIL, so it takes no lock.
+    _resident = {}
+
+    def __init__(self, M1, M2):
+        self.hyp = []
+        self.para = []
+        self._M1 = self._M2 = None
+        self.M2 = M2
+        self.M1 = M1
+
+    @property
+    def M1(self):
+        return self._M1
+
+    @M1.setter
+    def M1(self, value):
+        if value is not None:
+            value = np.asarray(value)
+            if value.ndim != 2:
+                raise Exception("cov.Pre: M1 must be a (train + 1) x test matrix")
+            if self._M2 is not None and value.shape[0] != self._M2.shape[0] + 1:
+                raise Exception("cov.Pre: M1 must have one row more than M2 (its last row holds the test self-covariances): "
+                                "M1 is %d x %d, M2 is %d x %d" % (value.shape + self._M2.shape))
+        self._M1 = value
+        self._tok1 = next(Pre._token_counter)
+
+    @property
+    def M2(self):
+        return self._M2
+
+    @M2.setter
+    def M2(self, value):
+        value = np.asarray(value)
+        if value.ndim != 2 or value.shape[0] != value.shape[1]:
+            raise Exception("cov.Pre: M2 must be a square (train x train) matrix, got shape %s" % (value.shape,))
+        if self._M1 is not None and self._M1.shape[0] != value.shape[0] + 1:
+            raise Exception("cov.Pre: M1 must have one row more than M2 (its last row holds the test self-covariances): "
+                            "M1 is %d x %d, M2 is %d x %d" % (self._M1.shape + value.shape))
+        self._M2 = value
+        self._tok2 = next(Pre._token_counter)
+        self._sym_checked = None
+
+    def _check_symmetric(self):
+        """The device program reads M2's lower triangle and mirrors it, the dense route and ``getCovMatrix`` use the whole
+        matrix: an asymmetric M2 would fit differently on the two.  Checked once per binding (per token), O(n^2)."""
+        if self._sym_checked != self._tok2:
+            if not np.allclose(self._M2, self._M2.T, rtol=1e-10, atol=1e-12 * float(np.max(np.abs(self._M2)))):
+                raise Exception("cov.Pre: M2 must be symmetric")
+            self._sym_checked = self._tok2
+
+    def touch(self):
+        """The arrays were changed in place: upload them again before the next fit / predict."""
+        self._tok1 = next(Pre._token_counter)
+        self._tok2 = next(Pre._token_counter)
+
+    def _check_train(self, x):
+        if x is not None and np.shape(x)[0] != self._M2.shape[0]:
+            raise Exception("cov.Pre: M2 is %d x %d but there are %d training inputs"
+                            % (self._M2.shape[0], self._M2.shape[1], np.shape(x)[0]))
+
+    def _check_test(self, z):
+        if self._M1 is None:
+            raise Exception("cov.Pre: no M1 (cross-covariances with the test points) was given")
+        if z is not None and np.shape(z)[0] != self._M1.shape[1]:
+            raise Exception("cov.Pre: M1 has %d columns but there are %d test inputs" % (self._M1.shape[1], np.shape(z)[0]))
+
+    def getCovMatrix(self, x=None, z=None, mode=None):
+        if mode == 'self_test':           # Core/cov.py:1443-1445
+            self._check_test(z)
+            A = self._M1[-1, :]
+            return np.reshape(A, (A.shape[0], 1))
+        if mode == 'train':               # :1446-1447
+            self._check_train(x)
+            return self._M2
+        if mode == 'cross':               # :1448-1449
+            self._check_train(x)
+            self._check_test(z)
+            return self._M1[:-1, :]
+        raise Exception("Specify the mode: 'train' or 'cross'")
+
+    def getDerMatrix(self, x=None, z=None, mode=None, der=None):
+        if der is not None:               # Core/cov.py:1453-1455
+            raise Exception("Error: NO optimization in precomputed kernel matrix")
+        return 0
+
+    def _pre_leaves(self):
+        return [self]
+
+    def _on_device(self):
+        return bool(self.device_leaf)
+
+    def _program(self, h0):
+        if not self.device_leaf:
+            return None
+        return [_lib.PROG_LEAF, int(self._kind), 0, 0, int(h0)], 1, 1, 0
+
+    def _bind_pre(self, ctx, test=False):
+        """Make context ``ctx`` hold this object's M2 (and, for predict, its M1).  Uploads only when the context holds
+        something else: another Pre's matrices, or this one's before a rebind / ``touch()``."""
+        key = ctx.value if hasattr(ctx, "value") else ctx
+        held = Pre._resident.setdefault(key, [None, None])
+        n = self._M2.shape[0]
+        if held[0] != self._tok2:
+            # (predict after another model used the context uploads M2 again although pgp_predict reads M1 alone: pgp_set_pre
+            # ties an M1 to the M2 of its n; one n^2 copy per switch between models, none while one model keeps the context)
+            self._check_symmetric()
+            held[0] = held[1] = None
+            _lib.check(_lib.load().pgp_set_pre(ctx, _lib.ptr(_lib.f64(self._M2)), n, None, 0), "pgp_set_pre")
+            held[0] = self._tok2
+        if test and held[1] != self._tok1:
+            held[1] = None
+            M1 = _lib.f64(self._M1)
+            _lib.check(_lib.load().pgp_set_pre(ctx, None, n, _lib.ptr(M1), M1.shape[1]), "pgp_set_pre")
+            held[1] = self._tok1
+
+    def _bind(self, ctx):
+        if not self.device_leaf:
+            raise NotImplementedError("pygps_amd: cov.Pre with device_leaf = False runs through the dense route only")
+        self._bind_pre(ctx)
+        return self._kind, 0, 0
+
+
+def refuse_pre(covfunc, what):
+    """FITC, sharded fits and GPMC have no meaning for / no code path with a precomputed matrix."""
+    if isinstance(covfunc, Kernel) and covfunc._pre_leaves():
+        raise NotImplementedError("pygps_amd: cov.Pre cannot be used with %s" % what)
+
+
 # ---- composites (Core/cov.py:230-328) ---------------------------------------------------------------------
 # A tree whose leaves all have isotropic device functors is evaluated in ONE pass of the tile kernel as a device
 # program (sum of products of leaf functors, csrc/sqdist_tile.h CovProgram) -- in getCovMatrix/getDerMatrix and,
@@ -416,6 +573,8 @@ class _Composite(Kernel):
         pr = self._program(0)
         if pr is None or pr[1] > _lib.PROG_MAX or pr[2] > _lib.PROG_MAX or pr[3] % 1000 > _lib.PROG_MAX or pr[3] >= 3000:
             return None                                   # too many leaves / products / Scale nodes, or more than two ARD leaves
+        if len(self._pre_leaves()) > 1:
+            return None                                   # more than one cov.Pre leaf
         return pr[0]
 
     def _bind(self, ctx):
@@ -426,14 +585,21 @@ class _Composite(Kernel):
                 "leaf, or more than %d leaves/products); there is no CPU fallback" % _lib.PROG_MAX)
         arr = (_lib.C.c_int32 * len(tok))(*tok)
         _lib.check(_lib.load().pgp_set_composite(ctx, arr, len(tok)), "pgp_set_composite")
+        for leaf in self._pre_leaves():                   # (one at most on this route) its M2 resident on the same context
+            leaf._bind_pre(ctx)
         return _lib.COV_COMPOSITE, 0, 0
 
     def _on_device(self):
         return self._tokens() is not None
 
+    def _matrices_on_device(self):
+        # a cov.Pre leaf is part of the device program of fits and predict; getCovMatrix / getDerMatrix of such a tree combine
+        # the children's matrices on the host (Pre slices its arrays, the other leaves are device-built)
+        return self._on_device() and not self._pre_leaves()
+
     def getCovMatrix(self, x=None, z=None, mode=None):
         self.checkInputGetCovMatrix(x, z, mode)
-        if self._on_device():
+        if self._matrices_on_device():
             return self._device_eval(x, z, mode, None)
         return self._host_cov(x, z, mode)
 
@@ -441,7 +607,7 @@ class _Composite(Kernel):
         self.checkInputGetDerMatrix(x, z, mode, der)
         if der >= len(self.hyp):
             raise Exception(self._WRONG_DER)
-        if self._on_device():
+        if self._matrices_on_device():
             return self._device_eval(x, z, mode, der)
         return self._host_der(x, z, mode, der)
 
@@ -463,6 +629,9 @@ class _Pair(_Composite):
         assert len(value) == n1 + len(self.cov2.hyp)
         self.cov1.hyp = list(value[:n1])
         self.cov2.hyp = list(value[n1:])
+
+    def _pre_leaves(self):
+        return self.cov1._pre_leaves() + self.cov2._pre_leaves()
 
     def _program(self, h0):
         a = self.cov1._program(h0)
@@ -523,6 +692,9 @@ class ScaleOfKernel(_Composite):
         self._scale = [value[0]]
         self.cov.hyp = list(value[1:])
 
+    def _pre_leaves(self):
+        return self.cov._pre_leaves()
+
     def _program(self, h0):
         a = self.cov._program(h0 + 1)
         if a is None:
@@ -544,6 +716,7 @@ class FITCOfKernel(Kernel):
     k(z, z).  inf.FITC_Exact does not call these (the whole fit is one device call); they exist for API parity."""
 
     def __init__(self, cov, inducingInput):
+        refuse_pre(cov, "the FITC approximation (fitc(u) of a precomputed matrix has no meaning)")
         self.inducingInput = np.asarray(inducingInput, dtype=float)
         self.covfunc = cov
         self.para = []

@@ -97,8 +97,12 @@ __device__ __forceinline__ const double* prog_ardw2(const CovProgram& P) { retur
 __device__ __forceinline__ const double* prog_ardw2(const CovParams&) { return nullptr; }
 __device__ __forceinline__ const double* prog_der_w(const CovProgram& P) { return cov_ard_der_w(P); }
 __device__ __forceinline__ const double* prog_der_w(const CovParams&) { return nullptr; }
-__device__ __forceinline__ double prog_elem(const CovProgram& P, double s, double dk2, bool same, double s1, double s2) { return cov_elem(P, s, dk2, same, s1, s2); }
-__device__ __forceinline__ double prog_elem(const CovParams& p, double s, double dk2, bool same, double, double) { return cov_elem(p, s, dk2, same); }
+__device__ __forceinline__ double prog_elem(const CovProgram& P, double s, double dk2, bool same, double s1, double s2, double pv) { return cov_elem(P, s, dk2, same, s1, s2, pv); }
+__device__ __forceinline__ double prog_elem(const CovParams& p, double s, double dk2, bool same, double, double, double) { return cov_elem(p, s, dk2, same); }
+__device__ __forceinline__ const double* prog_pre(const CovProgram& P) { return P.pre; }
+__device__ __forceinline__ const double* prog_pre(const CovParams&) { return nullptr; }
+__device__ __forceinline__ long prog_pre_ld(const CovProgram& P) { return P.pre_ld; }
+__device__ __forceinline__ long prog_pre_ld(const CovParams&) { return 0; }
 
 template <class COV> struct is_program { static constexpr bool value = false; };
 template <> struct is_program<CovProgram> { static constexpr bool value = true; };
@@ -237,8 +241,9 @@ __global__ __launch_bounds__(256) void cov_tile_kernel(const double* __restrict_
     constexpr int TS = ST + 2;                      // transpose-tile row stride (16-byte aligned rows)
     constexpr bool PROG = is_program<COV>::value;
     constexpr bool SMK = is_sm<COV>::value;         // D <= SKC: the one staged slab holds every coordinate of the tile
-    constexpr bool PARD = PROG && KIND >= 1;        // program with an ARD leaf: second (weighted) distance
-    constexpr bool PARD2 = PROG && KIND == 2;       // two ARD leaves: a third distance, kept in registers
+    constexpr bool PARD = PROG && (KIND & 3) >= 1;  // program with an ARD leaf: second (weighted) distance
+    constexpr bool PARD2 = PROG && (KIND & 3) == 2; // two ARD leaves: a third distance, kept in registers
+    constexpr bool PPRE = PROG && (KIND & 4) != 0;  // program with a precomputed-matrix leaf: its tile is loaded beside the distances
     constexpr int SMT = PARD ? 2 * 16 * 256 : (MODE == MODE_SYM ? ST * TS : (PROG ? 16 * 256 : 2));
     // coordinate slabs (2 x 16 x 64 doubles) and the mirror-transpose tile share one region: 33.8 KB -> 4 WGs per CU
     constexpr int SMX = 2 * SKC * ST;
@@ -294,6 +299,8 @@ __global__ __launch_bounds__(256) void cov_tile_kernel(const double* __restrict_
 #pragma unroll
             for (int e = 0; e < 16; ++e) { sv[e * 256] = s[e >> 2][e & 3]; if (PARD) sv1[e * 256] = s1[e >> 2][e & 3]; }
             const int pder = cov_ard_der(cp);           // derivative w.r.t. an ARD length-scale of the program's ARD leaf
+            double pm[PPRE ? 4 : 1][4];
+            if constexpr (PPRE) pre_tile_load(prog_pre(cp), prog_pre_ld(cp), r0, c0, pm);
 #pragma unroll 1
             for (int e = 0; e < 16; ++e) {
                 const int a = e >> 2, b = e & 3;
@@ -306,7 +313,9 @@ __global__ __launch_bounds__(256) void cov_tile_kernel(const double* __restrict_
                 }
                 double s2e = 0.0;
                 if constexpr (PARD2) s2e = sel16(s2, e);
-                sv[e * 256] = prog_elem(cp, sv[e * 256], dk2, MODE != MODE_RECT && r == c, PARD ? sv1[e * 256] : 0.0, s2e);
+                double pve = 0.0;
+                if constexpr (PPRE) pve = sel16(pm, e);
+                sv[e * 256] = prog_elem(cp, sv[e * 256], dk2, MODE != MODE_RECT && r == c, PARD ? sv1[e * 256] : 0.0, s2e, pve);
             }
 #pragma unroll
             for (int e = 0; e < 16; ++e) s[e >> 2][e & 3] = sv[e * 256];
@@ -884,7 +893,18 @@ static int cov_tile_dispatch(const CovSpec& cs, int train, long ntr, long ntc_, 
         for (int la : {pg.ard_leaf, pg.ard_leaf2})
             if (la >= 0 && pg.leaf[la].kind == 6 && pg.leaf[la].ref_der)
                 pg.leaf[la].gb = train == 1 ? 0.0 : cs.ell4;                      // Core/cov.py:1415-1418 as returned
-        if (pg.ard_leaf2 >= 0)
+        if (pg.pre_leaf >= 0) {
+            // the leaf's matrix: M2 on 'train', the caller's block of the transposed M1 on 'cross' (CovSpec::pre_cross, predict.hip)
+            pg.pre = train == 1 ? cs.pre_train : cs.pre_cross;
+            pg.pre_ld = cs.pre_ld;
+            if (!pg.pre || pg.pre_ld <= 0) return -14;
+            // every tile the kernel visits lies inside the padded resident matrix
+            if (train == 1 ? ntr * ST > cs.pre_rows || ntc_ * ST > cs.pre_ld : ntr * ST > cs.pre_cross_rows || ntc_ * ST > cs.pre_ld) return -14;
+#define PRE_LAUNCH(K) hipLaunchKernelGGL((cov_tile_kernel<MODE, CovProgram, K, false, false>), dim3(nblk), dim3(256), 0, st, XrT, ldr, n, \
+                                         XcT, ldc, m, dpad, pg, inv_sn2, out, ldo, tiles, ntiles, nt_)
+            if (pg.ard_leaf2 >= 0) PRE_LAUNCH(6); else if (pg.ard_leaf >= 0) PRE_LAUNCH(5); else PRE_LAUNCH(4);
+#undef PRE_LAUNCH
+        } else if (pg.ard_leaf2 >= 0)
             hipLaunchKernelGGL((cov_tile_kernel<MODE, CovProgram, 2, false, false>), dim3(nblk), dim3(256), 0, st, XrT, ldr, n,
                                XcT, ldc, m, dpad, pg, inv_sn2, out, ldo, tiles, ntiles, nt_);
         else if (pg.ard_leaf >= 0)
@@ -1012,6 +1032,27 @@ int cov_factor_panel_launch(const double* XT, long ldp, long n, long np, int dpa
 template <class COV>
 __global__ void cov_self_kernel(COV cp, int same, double* out) {
     if (threadIdx.x == 0 && blockIdx.x == 0) out[0] = cov_elem(cp, 0.0, 0.0, same != 0);
+}
+
+// Programs with a precomputed-matrix leaf: the diagonal differs from point to point.  out[j] = k_jj with the leaf's value
+// pre[j * stride] (train = 1: diag(M2), stride ld + 1; train = 2: the last row of M1, 'self_test');
+// sub: out[j] = max(k_jj - out[j], 0) -- the predictive variance from the column sums of squares already in out.
+__global__ __launch_bounds__(256) void cov_self_vec_kernel(CovProgram P, int same, const double* __restrict__ pre, long stride,
+                                                           long m, double* __restrict__ out, int sub) {
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= m) return;
+    const double k = cov_elem(P, 0.0, 0.0, same != 0, 0.0, 0.0, pre[j * stride]);
+    out[j] = sub ? fmax(k - out[j], 0.0) : k;
+}
+int cov_self_vec_launch(const CovSpec& cs, int train, const double* pre, long stride, long m, double* out_dev, int sub,
+                        hipStream_t st) {
+    if (!cs.has_pre() || !pre) return -14;
+    if (m <= 0) return PGP_OK;
+    CovProgram pg = cs.pg;
+    for (int l = 0; l < pg.nleaf; ++l) pg.leaf[l].train = train;
+    hipLaunchKernelGGL(cov_self_vec_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, pg, train == 1, pre, stride, m,
+                       out_dev, sub);
+    return hipGetLastError() == hipSuccess ? PGP_OK : PGP_ERR_HIP;
 }
 
 // train = 1: a diagonal entry of the training matrix; train = 2: 'self_test'

@@ -159,7 +159,7 @@ void pgp_destroy(pgp_ctx* c) { if (!c) return; GateShared device_gate_hold(c);
     for (auto& kv : c->spool) (void)hipFree(kv.second);
     for (auto& kv : c->orders) (void)hipFree(kv.second.first);
     void* bufs[] = {c->x_dev, c->y_dev, c->XsT, c->scale_dev, c->W, c->T, c->Binv, c->inv16, c->m_dev,
-                    c->rvec, c->zvec, c->partial, c->Dk, c->dpack, c->Xs, c->res_dev, c->prep};
+                    c->rvec, c->zvec, c->partial, c->Dk, c->dpack, c->Xs, c->res_dev, c->prep, c->pre2, c->pre1t, c->pre1s};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (c->res_host) (void)hipHostFree(c->res_host);
     if (c->in_host) (void)hipHostFree(c->in_host);
@@ -300,6 +300,7 @@ static int leaf_nhyp(int kind, long d) {
         case PGP_COV_RQARD: return (int)d + 2;
         case PGP_COV_RBFUNIT: case PGP_COV_NOISE: case PGP_COV_CONST: return 1;
         case PGP_COV_RQ: case PGP_COV_PERIODIC: return 3;
+        case PGP_COV_PRE: return 0;
         default: return -1;
     }
 }
@@ -343,6 +344,14 @@ static int make_leaf(int kind, const double* hyp, int nhyp, int para, int flags,
     return PGP_OK;
 }
 
+// A program with a cov.Pre leaf reads the context's resident M2 (pgp_set_pre), which must belong to the resident x
+static int bind_pre(pgp_ctx* c, CovSpec& cs) {
+    if (cs.pg.pre_leaf < 0) return PGP_OK;
+    if (!c || !c->pre2 || c->pre_n != c->n || c->n <= 0) return -14;
+    cs.pre_train = c->pre2; cs.pre_ld = c->pre_ld; cs.pre_rows = c->pre_ld;
+    return PGP_OK;
+}
+
 // Describe the covariance function of one call.  kind < PGP_COV_NKIND: a primitive; PGP_COV_COMPOSITE: the
 // postfix program registered with pgp_set_composite, expanded here into a sum of products.
 int make_spec(pgp_ctx* c, int kind, const double* hyp, int nhyp, int para, int flags, int der, long d, CovSpec& cs) {
@@ -380,10 +389,11 @@ int make_spec(pgp_ctx* c, int kind, const double* hyp, int nhyp, int para, int f
         CHK(make_leaf(kind, hyp, nhyp, para, flags, d, P.leaf[0], iso));
         if (der >= nhyp) return -4;
         P.nleaf = 1; P.nterm = 1; P.nscale = 0; P.is2[0] = iso * iso; P.hyp0[0] = 0; P.nh[0] = nhyp; P.ard_leaf = -1; P.ard_leaf2 = -1;
+        P.pre_leaf = kind == PGP_COV_PRE ? 0 : -1;
         P.coef[0] = 1.0; P.tl[0] = 1u; P.ts[0] = 0u;
         P.der = der; P.der_leaf = der >= 0 ? 0 : -1; P.der_j = der; P.der_scale = -1;
         cs.prog = true; cs.scale.assign(d, 1.0); cs.ncov = nhyp; cs.nder = nhyp;
-        return PGP_OK;
+        return bind_pre(c, cs);
     }
     if (kind != PGP_COV_COMPOSITE) {
         double iso;
@@ -415,7 +425,7 @@ int make_spec(pgp_ctx* c, int kind, const double* hyp, int nhyp, int para, int f
     CovProgram& P = cs.pg;
     P = CovProgram{};
     P.der = der; P.der_leaf = P.der_j = P.der_scale = -1;
-    P.ard_leaf = -1; P.ard_leaf2 = -1;
+    P.ard_leaf = -1; P.ard_leaf2 = -1; P.pre_leaf = -1;
     int used = 0;
     for (size_t i = 0; i < tok.size();) {
         const int op = tok[i];
@@ -429,6 +439,10 @@ int make_spec(pgp_ctx* c, int kind, const double* hyp, int nhyp, int para, int f
             if (nh < 0) return -2;
             if (h0 < 0 || h0 + nh > nhyp) return -11;
             if (P.nleaf >= CP_MAXLEAF) return -13;
+            if (lk == PGP_COV_PRE) {
+                if (P.pre_leaf >= 0) return -13;                                   // one precomputed-matrix leaf per program
+                P.pre_leaf = P.nleaf;
+            }
             double iso;
             CHK(make_leaf(lk, hyp + h0, nh, lpara, lflags, d, P.leaf[P.nleaf], iso));
             P.is2[P.nleaf] = iso * iso; P.hyp0[P.nleaf] = h0; P.nh[P.nleaf] = nh;
@@ -486,11 +500,14 @@ int make_spec(pgp_ctx* c, int kind, const double* hyp, int nhyp, int para, int f
         cs.ard_grad_diff = !(std::max(b1, b2) <= ARD_GRAM_GRAD_BOUND);
     }
     if (c && P.ard_leaf >= 0 && c->ard_grad_form) cs.ard_grad_diff = c->ard_grad_form == 2;
-    return PGP_OK;
+    return bind_pre(c, cs);
 }
 
 // value of the functor at zero distance: train = 1 -> K_ii (training diagonal), train = 2 -> k(z,z) of 'self_test'
 int cov_point_value(pgp_ctx* c, const CovSpec& cs, int train, double* out) {
+    // a cov.Pre leaf: K_ii and k(z,z) are vectors.  The fits read the training diagonal off the assembled K, pgp_predict takes
+    // k(z,z) from the last row of the bound M1 (cov_self_vec_launch); the one number is not used
+    if (cs.has_pre()) { *out = 0.0; return PGP_OK; }
     if (!cs.prog && cs.cp.der < 0) {          // every functor primitive has k(x,x) = sf2 (RBFunit: sf2 = 1)
         (void)train;
         *out = cs.cp.sf2;
@@ -1302,6 +1319,56 @@ int pgp_set_composite(pgp_ctx* c, const int32_t* prog, int nprog) { if (!c) retu
     return PGP_OK;
 }
 
+// cov.Pre (Core/cov.py:1429-1455): the precomputed matrices of the leaf, resident until replaced.  M2 (n, n) row-major goes into a
+// zero-padded np x np buffer (np = n rounded up to 128: every 64-tile the kernels visit is in bounds and 16-byte aligned);
+// M1 (n + 1, ns) is stored transposed, test-major -- row j = the n cross-covariances of test point j, the layout pgp_predict's
+// cross block reads along -- with its last row (the test self-covariances) as a vector of its own.  Either may be NULL: it is kept.
+int pgp_set_pre(pgp_ctx* c, const double* M2, int64_t n, const double* M1, int64_t ns) { if (!c) return -1; GateShared device_gate_hold(c);
+    if (!c) return -1;
+    if (n <= 0) return -3;
+    if (M1 && ns <= 0) return -5;
+    HIP_TRY(hipSetDevice(c->device));
+    (void)hipStreamSynchronize(c->st);
+    const long np = round_up(n, 128);
+    if (M2) {
+        if (c->pre2) (void)hipFree(c->pre2);
+        c->pre2 = nullptr; c->pre_n = 0;
+        if (c->pre1t) (void)hipFree(c->pre1t);                    // an M1 of another training set no longer applies
+        if (c->pre1s) (void)hipFree(c->pre1s);
+        c->pre1t = c->pre1s = nullptr; c->pre_ns = 0;
+        HIP_TRY(hipMalloc((void**)&c->pre2, (size_t)np * np * sizeof(double)));
+        HIP_TRY(hipMemsetAsync(c->pre2, 0, (size_t)np * np * sizeof(double), c->st));
+        HIP_TRY(hipMemcpy2DAsync(c->pre2, np * sizeof(double), M2, n * sizeof(double), n * sizeof(double), n, hipMemcpyHostToDevice, c->st));
+        HIP_TRY(hipStreamSynchronize(c->st));
+        c->pre_n = n; c->pre_ld = np;
+    }
+    if (M1) {
+        if (!c->pre2 || c->pre_n != n) return -2;
+        if (c->pre1t) (void)hipFree(c->pre1t);
+        if (c->pre1s) (void)hipFree(c->pre1s);
+        c->pre1t = c->pre1s = nullptr; c->pre_ns = 0;
+        const long nsp = round_up(ns, 128);
+        HIP_TRY(hipMalloc((void**)&c->pre1t, (size_t)nsp * np * sizeof(double)));
+        HIP_TRY(hipMalloc((void**)&c->pre1s, (size_t)nsp * sizeof(double)));
+        HIP_TRY(hipMemsetAsync(c->pre1t, 0, (size_t)nsp * np * sizeof(double), c->st));
+        HIP_TRY(hipMemsetAsync(c->pre1s, 0, (size_t)nsp * sizeof(double), c->st));
+        std::vector<double> blk;                                     // transposed on the host, 1024 test points at a time
+        for (int64_t a = 0; a < ns; a += 1024) {
+            const int64_t nb = std::min<int64_t>(1024, ns - a);
+            blk.resize((size_t)nb * n);
+            for (int64_t i = 0; i < n; ++i)
+                for (int64_t j = 0; j < nb; ++j) blk[(size_t)j * n + i] = M1[(size_t)i * ns + a + j];
+            HIP_TRY(hipMemcpy2DAsync(c->pre1t + a * np, np * sizeof(double), blk.data(), n * sizeof(double), n * sizeof(double), nb,
+                                     hipMemcpyHostToDevice, c->st));
+            HIP_TRY(hipStreamSynchronize(c->st));                    // blk is reused
+        }
+        HIP_TRY(hipMemcpyAsync(c->pre1s, M1 + (size_t)n * ns, ns * sizeof(double), hipMemcpyHostToDevice, c->st));
+        HIP_TRY(hipStreamSynchronize(c->st));
+        c->pre_ns = ns; c->pre_nsp = nsp;
+    }
+    return PGP_OK;
+}
+
 int pgp_set_data(pgp_ctx* c, const double* x, int64_t n, int64_t d, const double* y) { if (!c) return -1; GateShared device_gate_hold(c);
     if (!c) return -1;
     if (!x) return -2;
@@ -1554,6 +1621,7 @@ int pgp_cov(pgp_ctx* c, int kind, int mode, int der, const double* x, int64_t n,
     hipStream_t st = c->st;
     CovSpec cp;
     CHK(make_spec(c, kind, hyp, nhyp, para, flags, der, d, cp));
+    if (cp.has_pre()) return -13;                    // cov.Pre: getCovMatrix / getDerMatrix are host slices and sums (pygps_amd/cov.py)
     if (mode == PGP_MODE_SELF_TEST) {
         // zero distance: the functor itself gives value and derivatives (Core/cov.py:815-817, 924-925, 1163-1177,
         // SURVEY Q6), including the Matern derivative quirk and Noise = 0 on 'self_test' (cov.py:1271)

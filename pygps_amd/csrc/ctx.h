@@ -129,6 +129,10 @@ struct pgp_ctx {
     long n = 0, d = 0, np = 0, ldf = 0;
     int dpad = 0;
     double *x_dev = nullptr, *y_dev = nullptr, *XsT = nullptr, *scale_dev = nullptr;
+    // cov.Pre (pgp_set_pre): M2 zero-padded to pre_ld x pre_ld (pre_ld = pre_n rounded up to 128); M1 transposed, test-major
+    // (pre_nsp x pre_ld, pre_nsp = pre_ns rounded up to 128) and its last row, the test self-covariances (pre_nsp)
+    double *pre2 = nullptr, *pre1t = nullptr, *pre1s = nullptr;
+    long pre_n = 0, pre_ld = 0, pre_ns = 0, pre_nsp = 0;
     // fit workspace (sized for np)
     long ws_np = 0;
     double *W = nullptr, *T = nullptr, *Binv = nullptr, *inv16 = nullptr, *alpha_dev = nullptr, *m_dev = nullptr,

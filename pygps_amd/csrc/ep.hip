@@ -1174,6 +1174,7 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
     CHK(ensure_workspace(c, np));
     double kdiag = 0.0;                               // K_ii, identical for every training point (stationary kernels)
     double kss = 0.0;
+    const bool vdiag = dense || cp.has_pre();         // K_ii differs from point to point: read off the assembled K (a cov.Pre leaf: diag(M2))
     if (!dense) {
         CHK(cov_point_value(c, cp, 1, &kdiag));
         CHK(cov_point_value(c, cp, 2, &kss));
@@ -1251,9 +1252,9 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
     {   // the same per-site kernel with mu = 0, Sigma_ii = K_ii, zero site parameters: lZ_i = lik(y_i, m_i, K_ii)
         const long nbt = (n + 255) / 256;
         std::vector<double> ph(5 * nbt);
-        if (dense) EP_TRY(gather_strided_launch(w.Kd, np + 1, np, w.diag_d, st));          // K_ii differs from point to point
+        if (vdiag) EP_TRY(gather_strided_launch(w.Kd, np + 1, np, w.diag_d, st));          // K_ii differs from point to point
         hipLaunchKernelGGL(ep_site_terms_kernel, dim3((unsigned)nbt), dim3(256), 0, st, n, y_dev, w.m_d, (const double*)nullptr,
-                           dense ? (const double*)w.diag_d : (const double*)nullptr, kdiag, (const double*)nullptr, (const double*)nullptr,
+                           vdiag ? (const double*)w.diag_d : (const double*)nullptr, kdiag, (const double*)nullptr, (const double*)nullptr,
                            1, w.tmp_d, (double*)nullptr, lik, sn, (double*)nullptr);
         HIP_TRY(hipMemcpyAsync(ph.data(), w.tmp_d, ph.size() * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));

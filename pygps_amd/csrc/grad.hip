@@ -563,7 +563,9 @@ __global__ __launch_bounds__(256) void point_norm_kernel(const double* __restric
 // so that the leaf functors are instantiated once.
 // NARD: number of ARD leaves of the program (own weighted distances; per-dimension length-scale sums in a second pass
 // per leaf).  The second leaf's distance and weights stay in registers (sel16 / put16): static LDS ends at 64 KB.
-template <int NARD>
+// PRE: the program has a precomputed-matrix leaf (cov.Pre): its tile of the resident M2 is loaded with 16-byte loads beside the
+// distances; it has no hypers of its own but weights every other leaf's derivative and carries the Scale nodes above it.
+template <int NARD, bool PRE = false>
 __global__ __launch_bounds__(256) void hadamard_prog_kernel(const double* __restrict__ XT, long ldp, long n, int dpad,
                                                             CovProgram P, int ncov, double inv_sn2, double sn2,
                                                             const double* __restrict__ Binv, long ldb,
@@ -595,6 +597,9 @@ __global__ __launch_bounds__(256) void hadamard_prog_kernel(const double* __rest
 #pragma unroll
     for (int e = 0; e < 16; ++e) { sv[e * 256] = s[e >> 2][e & 3]; if (PARD) sv1[e * 256] = s1[e >> 2][e & 3]; }
 
+    double pm[PRE ? 4 : 1][4];
+    if constexpr (PRE) pre_tile_load(P.pre, P.pre_ld, r0, c0, pm);
+
     double gl[CP_MAXLEAF][3], gs[CP_MAXSCALE], tq = 0.0;
 #pragma unroll
     for (int l = 0; l < CP_MAXLEAF; ++l) gl[l][0] = gl[l][1] = gl[l][2] = 0.0;
@@ -617,12 +622,16 @@ __global__ __launch_bounds__(256) void hadamard_prog_kernel(const double* __rest
         const bool same = cc == rr;
         double v[CP_MAXLEAF], d[CP_MAXLEAF][3], T[CP_MAXTERM];
         double ardfac = 0.0, ardfac2 = 0.0;   // dK_l / d log ell_k = ardfac * (scaled squared difference in coordinate k)
+        double pve = 0.0;
+        if constexpr (PRE) pve = sel16(pm, e);
 #pragma unroll
         for (int l = 0; l < CP_MAXLEAF; ++l) {
             v[l] = 1.0; d[l][0] = d[l][1] = d[l][2] = 0.0;
             if (l < P.nleaf) {
                 const bool a1 = PARD && l == P.ard_leaf, a2 = PARD2 && l == P.ard_leaf2;
-                if (a1 || a2) {
+                if (PRE && l == P.pre_leaf) {
+                    v[l] = pve;                       // no hypers: d[l][.] stay zero
+                } else if (a1 || a2) {
                     // d[l][0]: magnitude hyper, d[l][1]: RQard shape hyper (Core/cov.py:922-936, 1412-1425)
                     double sl = sv1[e * 256];
                     if constexpr (PARD2) { if (a2) sl = sel16(s2, e); }
@@ -1095,7 +1104,14 @@ int hadamard_partial_launch(const double* XT, long ldp, long n, long np, int dpa
         CovProgram pg = cs.pg;
         for (int l = 0; l < pg.nleaf; ++l) pg.leaf[l].train = 1;
         if (cs.ard_grad_diff) mu = nullptr;           // the kernels' switch to the difference-form per-coordinate sums
-        if (pg.ard_leaf2 >= 0)
+        if (pg.pre_leaf >= 0) {
+            pg.pre = cs.pre_train; pg.pre_ld = cs.pre_ld;
+            if (!pg.pre || np > cs.pre_rows || np > cs.pre_ld) return -14;        // every tile lies inside the padded resident M2
+#define PRE_HLAUNCH(NA) hipLaunchKernelGGL((hadamard_prog_kernel<NA, true>), dim3((unsigned)nblk), dim3(256), 0, st, XT, ldp, n, dpad, pg, \
+                                           ncov, 1.0 / sn2, sn2, Binv, ldb, alpha, wv, partial, nt, mu, b0)
+            if (pg.ard_leaf2 >= 0) PRE_HLAUNCH(2); else if (pg.ard_leaf >= 0) PRE_HLAUNCH(1); else PRE_HLAUNCH(0);
+#undef PRE_HLAUNCH
+        } else if (pg.ard_leaf2 >= 0)
             hipLaunchKernelGGL(hadamard_prog_kernel<2>, dim3((unsigned)nblk), dim3(256), 0, st, XT, ldp, n, dpad, pg, ncov,
                                1.0 / sn2, sn2, Binv, ldb, alpha, wv, partial, nt, mu, b0);
         else if (pg.ard_leaf >= 0)

@@ -31,6 +31,8 @@ int cov_factor_launch(const double* XT, long ldp, long n, long np, int dpad, con
 int cov_factor_panel_launch(const double* XT, long ldp, long n, long np, int dpad, const CovSpec& cs, double inv_sn2,
                             long col0, long ncols, double* panel, long ldpanel, hipStream_t st);
 int cov_self_launch(const CovSpec& cs, int train, double* out_dev, hipStream_t st);
+int cov_self_vec_launch(const CovSpec& cs, int train, const double* pre, long stride, long m, double* out_dev, int sub,
+                        hipStream_t st);
 int self_fill_launch(double* out, long m, double val, hipStream_t st);
 
 // grad.hip

@@ -230,7 +230,11 @@ int pgp_predict(pgp_ctx* c, pgp_factor* f, const double* xs, int64_t ns, const d
     const long np = f->np, n = f->n;
     const int d = f->d, dpad = f->dpad;
     // the product form (W = L^-1, one GEMM per batch) or the blocked solve: see predict_batch_product
-    const bool product = np >= 1024 && (c->predict_inverse == 2 || (c->predict_inverse == 1 && (f->Linv != nullptr || f->Eraw != nullptr || ns >= 1024)));
+    // a cov.Pre leaf: the cross block comes from the M1 bound to this context (pgp_set_pre), which must be this model's -- n training
+    // points, ns test points.  It is stored test-major, the orientation of the blocked solve's cross block, so that form serves
+    const bool pre = f->cs.has_pre();
+    if (pre && (!c->pre1t || !c->pre1s || c->pre_n != n || c->pre_ns != ns || c->pre_ld != np)) return -15;
+    const bool product = !pre && np >= 1024 && (c->predict_inverse == 2 || (c->predict_inverse == 1 && (f->Linv != nullptr || f->Eraw != nullptr || ns >= 1024)));
     if (product) CHK(ensure_linv(c, f));
     else CHK(ensure_wd(c, f));
     // test points per batch (the reference uses 1000): up to predict_batch = 65536 within 16 GiB of scratch, so that the K = 128
@@ -282,6 +286,7 @@ int pgp_predict(pgp_ctx* c, pgp_factor* f, const double* xs, int64_t ns, const d
             HIP_TRY(hipMemcpyAsync(msd, h_ms, nb_ * sizeof(double), hipMemcpyHostToDevice, st));
         } else HIP_TRY(hipMemsetAsync(msd, 0, nb_ * sizeof(double), st));
         CHK(scale_transpose_launch(xd, nb_, d, scd, XcT, ldc, dpad, st));
+        if (pre) { cp.pre_cross = c->pre1t + a * c->pre_ld; cp.pre_ld = c->pre_ld; cp.pre_cross_rows = c->pre_nsp - a; }
         if (product) CHK(predict_batch_product(c, f, cp, XcT, ldc, nb_, nrhs, msd, Ks, Vp, part, o1, o2, st));
         else {
         // Ks as column-major (np x nrhs): rows = test points, columns = training points in the tile kernel's view
@@ -290,6 +295,10 @@ int pgp_predict(pgp_ctx* c, pgp_factor* f, const double* xs, int64_t ns, const d
         CHK(col_dot_full_launch(Ks, np, n, nb_, f->alpha, msd, o1, st));                  // fmu = ms + Ks' alpha
         if (f->sWv) CHK(row_scale_launch(Ks, np, n, nrhs, f->sWv, st));                   // EP: sW o Ks
         CHK(solve_lower_multi(c, f->F, f->ldf, f->Wd, Ks, np, np, nrhs, false));
+        if (pre) {                               // k(z,z) differs per test point: raw sums of squares, then max(k_jj - s_j, 0)
+            CHK(col_sumsq_launch(Ks, np, n, nb_, 0.0, -(f->sWv ? 1.0 : f->sw * f->sw), o2, st));
+            CHK(cov_self_vec_launch(cp, 2, c->pre1s + a, 1, nb_, o2, 1, st));
+        } else
         CHK(col_sumsq_launch(Ks, np, n, nb_, f->kss, f->sWv ? 1.0 : f->sw * f->sw, o2, st));
         }
         HIP_TRY(hipMemcpyAsync(h_o1, o1, nb_ * sizeof(double), hipMemcpyDeviceToHost, st));

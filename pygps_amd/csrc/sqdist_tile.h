@@ -50,6 +50,12 @@ struct CovProgram {
     double ardw[CP_MAXARD];          // weighted sum_k ardw[k] (x_k - z_k)^2, ardw[k] = 1 / ell_k^2, accumulated beside r^2
     int ard_leaf2;                   // a second ARD leaf with its own weights (-1: none): at most two per program
     double ardw2[CP_MAXARD];
+    // a precomputed-matrix leaf (cov.Pre, Core/cov.py:1429-1455; -1: none, at most one per program).  Its value is not a function
+    // of the distance: element (row r, column c) of the tile kernels' view is pre[r * pre_ld + c] of a context-owned, zero-padded
+    // resident matrix (pgp_set_pre): M2 on 'train', the test-major transpose of M1 at the batch's offset on 'cross'.  No hypers.
+    int pre_leaf;
+    const double* pre;
+    long pre_ld;
 };
 
 // Spectral mixture kernel (Wilson & Adams 2013; Core/cov.py:454-619, GPML covSM with the product over the coordinates):
@@ -548,6 +554,11 @@ struct CovSpec {
     int gram_fast = 2;              // Gram-form assembly: 0 the general kernel, 1 the restructured one, 2 + its four-workgroups-per-CU form at d = 64
     int gram_grid = 32768;          // Gram-form assembly: persistent workgroups per launch (option "gram_grid")
     double sf2() const { return cp.sf2; }
+    // the resident matrices of a cov.Pre leaf (device, owned by the context: pgp_set_pre), filled in by make_spec / pgp_predict
+    const double* pre_train = nullptr;   // M2, zero-padded to pre_rows x pre_ld
+    const double* pre_cross = nullptr;   // rows = test points of the current predict batch, columns = training points (same pre_ld)
+    long pre_ld = 0, pre_rows = 0, pre_cross_rows = 0;
+    bool has_pre() const { return prog && pg.pre_leaf >= 0; }      // a cov.Pre leaf: the diagonal and k(z,z) differ from point to point
 };
 
 // the spectral mixture description of a spec with its derivative index (cp.der, hyp layout of CovSM::h) resolved
@@ -600,10 +611,31 @@ __device__ __forceinline__ double prog_leaf_dist(const CovProgram& P, int l, dou
     return l == P.ard_leaf ? s1 : (l == P.ard_leaf2 ? s2 : r2 * P.is2[l]);
 }
 
-__device__ __forceinline__ double prog_value(const CovProgram& P, double r2, bool same, double s1 = 0.0, double s2 = 0.0) {
+// The 64 x 64 tile of a program's precomputed-matrix leaf (cov.Pre) in the thread layout of sqdist_tile: eight 16-byte loads per
+// thread, the 16 threads of one tile row reading 256 contiguous bytes.  The resident matrix is zero-padded to whole tiles and its
+// leading dimension is a multiple of 128 doubles (pgp_set_pre), so every load is aligned and in bounds.
+__device__ __forceinline__ void pre_tile_load(const double* __restrict__ pre, long ld, long r0, long c0, double (&pm)[4][4]) {
+    const int t = threadIdx.x, tr = t >> 4, tc = t & 15;
+    const double* pb = pre + (r0 + 4 * tr) * ld + c0 + 2 * tc;
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int bh = 0; bh < 2; ++bh) {
+            const double2_t q = *(const double2_t*)(pb + (long)a * ld + 32 * bh);
+            pm[a][2 * bh] = q[0]; pm[a][2 * bh + 1] = q[1];
+        }
+}
+
+// pv: the element's value of the precomputed-matrix leaf (P.pre_leaf), loaded by the caller
+__device__ __forceinline__ double prog_leaf_value(const CovProgram& P, int l, double r2, bool same, double s1, double s2, double pv) {
+    return l == P.pre_leaf ? pv : cov_value<true>(P.leaf[l], prog_leaf_dist(P, l, r2, s1, s2), same);
+}
+
+__device__ __forceinline__ double prog_value(const CovProgram& P, double r2, bool same, double s1 = 0.0, double s2 = 0.0,
+                                             double pv = 0.0) {
     double v[CP_MAXLEAF], T[CP_MAXTERM];
 #pragma unroll
-    for (int l = 0; l < CP_MAXLEAF; ++l) v[l] = l < P.nleaf ? cov_value<true>(P.leaf[l], prog_leaf_dist(P, l, r2, s1, s2), same) : 1.0;
+    for (int l = 0; l < CP_MAXLEAF; ++l) v[l] = l < P.nleaf ? prog_leaf_value(P, l, r2, same, s1, s2, pv) : 1.0;
     prog_terms(P, v, T);
     double K = 0.0;
 #pragma unroll
@@ -614,10 +646,10 @@ __device__ __forceinline__ double prog_value(const CovProgram& P, double r2, boo
 // derivative matrix entry for the flat hyper index P.der (Product :246-256, Sum :281-291, Scale :320-328)
 // dk2: ARD-weighted squared difference in coordinate der_j (only when the derivative is w.r.t. an ARD length-scale)
 __device__ __forceinline__ double prog_deriv(const CovProgram& P, double r2, bool same, double s1 = 0.0, double dk2 = 0.0,
-                                             double s2 = 0.0) {
+                                             double s2 = 0.0, double pv = 0.0) {
     double v[CP_MAXLEAF], T[CP_MAXTERM];
 #pragma unroll
-    for (int l = 0; l < CP_MAXLEAF; ++l) v[l] = l < P.nleaf ? cov_value<true>(P.leaf[l], prog_leaf_dist(P, l, r2, s1, s2), same) : 1.0;
+    for (int l = 0; l < CP_MAXLEAF; ++l) v[l] = l < P.nleaf ? prog_leaf_value(P, l, r2, same, s1, s2, pv) : 1.0;
     if (P.der_scale >= 0) {               // 2 * exp(h) * child, through whatever sits above the Scale node
         prog_terms(P, v, T);
         double K = 0.0;
@@ -643,8 +675,8 @@ __device__ __forceinline__ double cov_elem(const CovParams& p, double s, double 
     return p.der < 0 ? cov_value(p, s, same) : cov_deriv(p, s, dk2, same);
 }
 __device__ __forceinline__ double cov_elem(const CovProgram& P, double s, double dk2, bool same, double s1 = 0.0,
-                                           double s2 = 0.0) {
-    return P.der < 0 ? prog_value(P, s, same, s1, s2) : prog_deriv(P, s, same, s1, dk2, s2);
+                                           double s2 = 0.0, double pv = 0.0) {
+    return P.der < 0 ? prog_value(P, s, same, s1, s2, pv) : prog_deriv(P, s, same, s1, dk2, s2, pv);
 }
 __device__ __forceinline__ int cov_ard_der(const CovParams& p) { return (cov_is_ard(p) && p.der >= 0 && p.der < p.D) ? p.der : -1; }
 __device__ __forceinline__ int cov_ard_der(const CovProgram& P) {

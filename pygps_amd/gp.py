@@ -65,6 +65,8 @@ class GP(object):
         if kernel is not None:
             assert isinstance(kernel, cov.Kernel), "cov function is not an instance of pygps_amd.cov.Kernel"
             self.covfunc = kernel
+            if type(kernel) is cov.Pre:                    # a precomputed matrix alone keeps the model's zero mean (Core/gp.py:221-222)
+                self.usingDefaultMean = False
 
     def setOptimizer(self, method, num_restarts=None, min_threshold=None, meanRange=None, covRange=None, likRange=None):
         conf_ = None
@@ -156,6 +158,10 @@ class GP(object):
             _lib.check(_lib.load().pgp_predict_dense(L.ctx, L.handle, _lib.ptr(Ks), ns, _lib.ptr(kss), _lib.ptr(ms), _lib.ptr(fmu),
                                                      _lib.ptr(fs2)), "pgp_predict_dense")
             return fmu.reshape(ns, 1), fs2.reshape(ns, 1)
+        for leaf in self.covfunc._pre_leaves():            # cov.Pre: the M1 the cross block is read from must be THIS model's,
+            leaf._check_train(self.x)                      # whatever the context held last (another model may have fitted since)
+            leaf._check_test(xs)
+            leaf._bind_pre(L.ctx, test=True)
         rc = _lib.load().pgp_predict(L.ctx, L.handle, _lib.ptr(xs), ns, _lib.ptr(ms), _lib.ptr(fmu), _lib.ptr(fs2))
         if rc == -99:
             raise NotImplementedError("pygps_amd: the device predict path is not built in this version")
@@ -539,6 +545,7 @@ class GPMC(object):
         row = test point, column = class  (Core/gp.py:829-863)."""
         if xs.ndim == 1:
             xs = np.reshape(xs, (xs.shape[0], 1))
+        cov.refuse_pre(self._prior()[1], "GPMC (every pair of classes fits on its own subset of x)")
         self._check_classes()
         self.pair_nlZ, self.pair_iters, self.pair_hyp = {}, {}, {}
         if self.choose_route(xs.shape[0]) == "shared":
@@ -551,6 +558,7 @@ class GPMC(object):
         reference; without one every pair starts from GPC's defaults."""
         if xs.ndim == 1:
             xs = np.reshape(xs, (xs.shape[0], 1))
+        cov.refuse_pre(self._prior()[1], "GPMC (every pair of classes fits on its own subset of x)")
         self._check_classes()
         self.pair_nlZ, self.pair_iters, self.pair_hyp = {}, {}, {}
         return self._by_pairs(xs, optimize=True)

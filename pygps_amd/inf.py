@@ -214,6 +214,19 @@ def _device_kernel(covfunc, ctx):
     return covfunc._bind(ctx)
 
 
+def _dense_route(covfunc):
+    """True for covariance functions that are not device programs: K and the derivative matrices come from getCovMatrix /
+    getDerMatrix.  Trees over the program limits -- and every tree that holds a cov.Pre with ``device_leaf = False``."""
+    return isinstance(covfunc, (_cov._Composite, _cov.Pre)) and not covfunc._on_device()
+
+
+def _check_pre(covfunc, x):
+    """cov.Pre leaves: M2 must be the matrix of these training inputs."""
+    if isinstance(covfunc, _cov.Kernel):
+        for leaf in covfunc._pre_leaves():
+            leaf._check_train(x)
+
+
 def _mean_inputs(meanfunc, x):
     n = x.shape[0]
     m = _lib.f64(meanfunc.getMean(x)).reshape(n)
@@ -321,7 +334,10 @@ class Exact(Inference):
     def evaluate(self, meanfunc, covfunc, likfunc, x, y, nargout=1):
         if not isinstance(likfunc, _lik.Gauss):
             raise Exception("Exact inference only possible with Gaussian likelihood")
-        if isinstance(covfunc, _cov._Composite) and not covfunc._on_device():
+        if self.sharded:
+            _cov.refuse_pre(covfunc, "a sharded fit (the panels of a distributed factor are assembled per rank)")
+        _check_pre(covfunc, x)
+        if _dense_route(covfunc):
             if self.sharded:
                 raise NotImplementedError("pygps_amd: a sharded fit needs a covariance function that runs as a device program")
             return self._evaluate_dense(meanfunc, covfunc, likfunc, x, y, nargout)
@@ -396,7 +412,8 @@ class EP(Inference):
         # covariance functions that are not device programs (Core/cov.py:230-328 composes anything): K and the derivative
         # matrices come from getCovMatrix / getDerMatrix, the sweeps, the posterior, alpha, nlZ and every Hadamard sum
         # 1/2 sum((sW sW' o B^-1 - alpha alpha') o dK_h) (Core/inf.py:780-786) run on the device
-        dense = isinstance(covfunc, _cov._Composite) and not covfunc._on_device()
+        _check_pre(covfunc, x)
+        dense = _dense_route(covfunc)
         if not dense:
             kind, para, flags = _device_kernel(covfunc, _lib.ctx(dev))
         x = _lib.f64(x)
@@ -495,7 +512,8 @@ class Laplace(Inference):
     def evaluate(self, meanfunc, covfunc, likfunc, x, y, nargout=1):
         lik, likhyp, nlik = self._lik_args(likfunc)
         dev = _lib.default_device() if self.device is None else self.device
-        dense = isinstance(covfunc, _cov._Composite) and not covfunc._on_device()
+        _check_pre(covfunc, x)
+        dense = _dense_route(covfunc)
         if not dense:
             kind, para, flags = _device_kernel(covfunc, _lib.ctx(dev))
         x = _lib.f64(x)
@@ -601,6 +619,7 @@ class FITC_Exact(Inference):
             raise Exception('Exact inference only possible with Gaussian likelihood')
         if not isinstance(covfunc, _cov.FITCOfKernel):
             raise Exception('Only covFITC supported.')
+        _cov.refuse_pre(covfunc.covfunc, "the FITC approximation (fitc(u) of a precomputed matrix has no meaning)")
         dev = _lib.default_device() if self.device is None else self.device
         kind, para, flags = _device_kernel(covfunc.covfunc, _lib.ctx(dev))
         x = _lib.f64(x)
@@ -667,6 +686,7 @@ class FITC_EP(Inference):
     def evaluate(self, meanfunc, covfunc, likfunc, x, y, nargout=1):
         if not isinstance(covfunc, _cov.FITCOfKernel):
             raise NotImplementedError("pygps_amd: FITC_EP needs a FITC covariance (covfunc.fitc(u)); only covFITC is supported")
+        _cov.refuse_pre(covfunc.covfunc, "the FITC approximation (fitc(u) of a precomputed matrix has no meaning)")
         if isinstance(likfunc, _lik.Laplace):
             lik, likhyp = _lib.LIK_LAPLACE, _lib.f64(np.asarray(likfunc.hyp, dtype=float).reshape(-1))
         elif isinstance(likfunc, _lik.Erf):
