@@ -203,6 +203,7 @@ int pgp_set_option(pgp_ctx* c, const char* name, int value) {
     if (!strcmp(name, "s_pan")) { if (value < -1 || value > 2) return -2; c->s_pan = value; return PGP_OK; }
     if (!strcmp(name, "s_pan_direct")) { c->s_pan_direct = value != 0; return PGP_OK; }
     if (!strcmp(name, "s_pan_out")) { c->s_pan_out = value != 0; return PGP_OK; }
+    if (!strcmp(name, "skip_zeros")) { c->skip_zeros = value != 0; return PGP_OK; }
     if (!strcmp(name, "tud_mark")) { c->tud_mark = value != 0; return PGP_OK; }
     if (!strcmp(name, "sched2_wide")) { c->sched2_wide = value != 0; return PGP_OK; }
     if (!strcmp(name, "gram_assembly")) { if (value < 0 || value > 2) return -2; c->gram_assembly = value; return PGP_OK; }
@@ -841,6 +842,17 @@ static int solve_below(pgp_ctx* c, const SweepMat& m, int s0, int s1, const doub
     return gemm_prof(c, PC_GEMM_SOLVE, g, st);
 }
 
+// Option skip_zeros: the panel's own inverse rows (rows >= g.zero_from) hold E_D = L_D^-T, upper triangular, so tile row r of them
+// starts at k = T r (GemmArgs::zf_upper; T = the tile's rows) instead of multiplying the zeros left of the diagonal -- eet_panel_args
+// clips the same structure with KM_GE_I.  g.flops stays what is EXECUTED: the skipped products come off.
+static void trailing_skip(pgp_ctx* c, GemmArgs& g) {
+    if (!c->skip_zeros || g.zero_from <= 0 || g.zero_from >= g.M) return;
+    const int T = g.tile == 64 ? 64 : 128;
+    g.zf_upper = 1;
+    const double nr = (double)((g.M - g.zero_from) / T);
+    g.flops -= (double)T * T * g.N * nr * (nr - 1.0);                // sum_r 2 T N (T r)
+}
+
 // TU: C[rows >= c0, cols c0..c1) -= P P^T, P = solved columns [k0, k1); out != nullptr: result goes to the staging buffer
 static GemmArgs trailing_update2_args(pgp_ctx* c, const SweepMat& m, int k0, int k1, int c0, int c1, double* out, long ldx) {
     const long r0 = (long)c0 * 128, r1 = m.mrows + m.rows2(k1);
@@ -866,6 +878,7 @@ static GemmArgs trailing_update2_args(pgp_ctx* c, const SweepMat& m, int k0, int
     const long t128 = (long)(g.M / 128) * (g.N / 128) - (long)(g.N / 128) * (g.N / 128 - 1) / 2;
     g.tile = t128 < c->small_tile_below ? 64 : 128;
     g.flops = 2.0 * (double)g.K * ((double)g.M * g.N - 0.5 * (double)g.N * g.N);
+    trailing_skip(c, g);
     return g;
 }
 // TU_a in two pieces (sched 2): columns [c0, c1) <- C - P P^T restricted to the row blocks [rb0, rb1) (rb1 < 0: to the last row
@@ -892,6 +905,7 @@ static GemmArgs trailing_update_rows_args(pgp_ctx* c, const SweepMat& m, int k0,
     if (split && !m.dense2) g.zero_from = (int)(m.mrows + (long)k0 * 128 - r0);
     g.tile = tile;
     g.flops = 2.0 * (double)g.K * ((double)g.M * g.N - (rb0 == c0 ? 0.5 * (double)g.N * g.N : 0.0));
+    trailing_skip(c, g);
     return g;
 }
 

@@ -67,6 +67,10 @@ struct GemmArgs {
     int rev_rows;           // ... tile rows last-to-first (KM_LT_I: the long-k tiles start first)
     int fold_rows;          // plain LDS-DMA 128-tile rectangles: one workgroup runs the tile rows mt - 1 - r AND r (gemm_f64_fold_kernel)
     int zero_from;          // > 0: tile rows i0 >= zero_from take beta = 0 (rows touched for the first time: never read)
+    int zf_upper;           // with zero_from: rows i >= zero_from of the A operand are upper-trapezoidal, A(i, k) == 0 for k < i - zero_from
+                            // (a panel's own inverse rows E_D = L_D^-T in a trailing update): a tile of those rows starts its k-range at
+                            // i0 - zero_from instead of multiplying the zeros (every skipped product has an exact +-0 factor and the
+                            // accumulators start at +0: same bits)
     // Batched launches whose products shrink with the batch index z (the owned column panels of a block-cyclic sweep):
     // product z has M - z * batch_dm rows (tiles beyond them exit at once) and its first-touch row moves up with it.
     int batch_dm;

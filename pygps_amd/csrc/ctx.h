@@ -84,6 +84,9 @@ struct pgp_ctx {
                                         // 6144 5.71 -> 5.61, 5120 neutral, 4096 2.84 -> 2.78
     int s_pan_direct = 1;               // s_pan: TU_d(p) waits for the paired launch of panel p - 1 by its own event (0: through the main stream)
     int s_pan_out = 1;                  // s_pan: D(p)'s stage-out on the main stream beside S(p) instead of on the chain (scratch double-buffered)
+    int skip_zeros = 1;                 // trailing updates: the tiles of a panel's own inverse rows (E_D = L_D^-T, upper triangular) start their k-range at
+                                        // the row's diagonal instead of multiplying the zeros left of it (GemmArgs::zf_upper): 2.1 % of the MFMA work
+                                        // of an N = 8192 fit, same bits; 0 = the full k-range
     int tud_mark = 1;                   // sched 2: that piece marks its CUs like the chain's own products (yield role 2)
     int leaf_pivot = 2;                 // 2: register-resident leaf (panel.hip leaf_potrf_reg_kernel); 1: the LDS leaf with its 16 x 16 pivot blocks on
                                         // the matrix cores (pivot_block_mfma); 0: the LDS leaf, pivot blocks lane per row

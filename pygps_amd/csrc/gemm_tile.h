@@ -82,6 +82,9 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, int ti, int tj, lon
     else if (g.kmode == KM_GE_J) k0 = j0 + koff;
     else if (g.kmode == KM_LT_I) k1 = i0 + TM + koff;
     else if (g.kmode == KM_LT_J) k1 = j0 + TN + koff;
+    // first-touch rows that are upper-trapezoidal in A (GemmArgs::zf_upper): A(i, k) == 0 for k < i - zero_from, so the tile's
+    // k-range starts at its first row's diagonal (a multiple of the tile size: whole LDS-DMA stages).  These tiles never read C
+    if (g.zf_upper && zero_from > 0 && i0 >= zero_from && i0 - zero_from > k0) k0 = i0 - zero_from;
     if (k0 < 0) k0 = 0;
     if (k1 > g.K) k1 = g.K;
     k0 &= ~(BK - 1);

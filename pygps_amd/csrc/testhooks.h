@@ -13,6 +13,11 @@ int pgp_test_gemm(pgp_ctx* ctx, int tile, int a_kc, int b_kc, int tri, int mask_
                   double* C, int64_t ldc, int M, int N, int K, int iters, double* ms_out);
 int pgp_test_gemm_shrink(pgp_ctx* ctx, const double* Y, int64_t ldy, int M, int K, int w, int nb, int dm, int zero_from,
                          double* C, int64_t ldc, int64_t sC);
+/* C = beta Cin + alpha A B' (Cin NULL: in place) with the k-clip of the trailing updates: first-touch rows from zero_from on,
+   upper-trapezoidal there when zf_upper is set. */
+int pgp_test_gemm_zskip(pgp_ctx* ctx, int tile, int tri, int mask_diag, int zero_from, int zf_upper, double alpha, double beta,
+                        const double* A, int64_t lda, const double* B, int64_t ldb, const double* Cin, double* C, int64_t ldc,
+                        int M, int N, int K);
 /* C -= A B' on the lower tiles (packed, masked diagonal tiles) but those whose first row and column lie in [skip_lo, skip_hi); with
    wait_ms > 0 every workgroup waits inside the kernel for a device counter that the second stream raises wait_ms later. */
 int pgp_test_gemm_skip_wait(pgp_ctx* ctx, int tile, const double* A, const double* B, double* C, int n, int K, int skip_lo,

@@ -557,6 +557,36 @@ int pgp_test_gemm_shrink(pgp_ctx* ctx, const double* Y, int64_t ldy, int M, int 
     return PGP_OK;
 }
 
+// The k-clip of the trailing updates on one product  C = beta Cin + alpha A B'  (host buffers, column-major, A and B M-contiguous):
+// first-touch rows from zero_from on, upper-trapezoidal there with zf_upper (GemmArgs::zf_upper: the k-range of those tiles starts at
+// the row's diagonal).  Cin == NULL: in place.
+int pgp_test_gemm_zskip(pgp_ctx* ctx, int tile, int tri, int mask_diag, int zero_from, int zf_upper, double alpha, double beta,
+                        const double* A, int64_t lda, const double* B, int64_t ldb, const double* Cin, double* C, int64_t ldc,
+                        int M, int N, int K) {
+    if (!ctx) return -1;
+    pgp_ctx* c = ctx;
+    if (!A || !B || !C || M <= 0 || N <= 0 || M % 128 || N % 128 || K % 16 || lda < M || ldb < N || ldc < M) return -2;
+    if ((tile != 64 && tile != 128) || zero_from < 0 || zero_from % 128) return -2;
+    HIP_TRY(hipSetDevice(c->device));
+    DevScratch scr;
+    double *Ad = nullptr, *Bd = nullptr, *Cd = nullptr, *Ci = nullptr;
+    const size_t an = (size_t)lda * K * 8, bn = (size_t)ldb * K * 8, cn = (size_t)ldc * N * 8;
+    CHK(scr.alloc(&Ad, an)); CHK(scr.alloc(&Bd, bn)); CHK(scr.alloc(&Cd, cn));
+    HIP_TRY(hipMemcpy(Ad, A, an, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(Bd, B, bn, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(Cd, C, cn, hipMemcpyHostToDevice));
+    if (Cin) { CHK(scr.alloc(&Ci, cn)); HIP_TRY(hipMemcpy(Ci, Cin, cn, hipMemcpyHostToDevice)); }
+    GemmArgs g{};
+    g.A = Ad; g.lda = lda; g.B = Bd; g.ldb = ldb; g.C = Cd; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.alpha = alpha; g.beta = beta;
+    if (Ci) { g.Cin = Ci; g.ldcin = ldc; }
+    g.tri = tri; g.mask_diag = mask_diag; g.kmode = KM_FULL; g.batch = 1; g.tile = tile; g.dbg = c->gemm_dbg;
+    g.zero_from = zero_from; g.zf_upper = zf_upper;
+    const int rc = gemm_f64_launch(g, c->st);
+    HIP_TRY(hipStreamSynchronize(c->st));
+    if (rc == PGP_OK) HIP_TRY(hipMemcpy(C, Cd, cn, hipMemcpyDeviceToHost));
+    return rc;
+}
+
 }  // extern "C"
 
 // ---- dispatcher experiment (tools/slot_probe.py): does a small high-LDS kernel on a second stream find the CUs that a resident
