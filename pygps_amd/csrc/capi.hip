@@ -1,6 +1,5 @@
-// C ABI (include/pygps_amd.h) + host-side drivers: blocked right-looking Cholesky with a two-level
-// panel (outer K = 512 trailing updates on the fp64 MFMA GEMM, inner 128-wide leaves), recursive
-// triangular inverse, W^T W, fused gradient reduce.  See DESIGN.md for the pipeline.
+// C ABI (include/pygps_amd.h) + host-side drivers: the exact fit around the Cholesky sweep (sweep.hip), GEMM launch
+// bookkeeping and tile-order tables, recursive triangular inverse, W^T W, fused gradient reduce.  See DESIGN.md for the pipeline.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -656,9 +655,9 @@ static int gemm_prepare(pgp_ctx* c, GemmArgs& g) {
     if (xcd) CHK(tile_order(c, g.M / 128, g.N / 128, g.tri, g.tri ? g.tri_off / 128 : 0, &g.order, &g.norder));
     if (c->yield && c->yield_flags) {
         g.yield_flags = c->yield_flags;
-        // the chain's own small products mark their CUs; every bulk (128-tile, LDS-DMA) launch polls
-        g.yield_role = c->chain_now ? 2 : (gemm_f64_uses_dma(g) ? 1 : 0);
-    }
+        // the chain's own small products mark their CUs (the caller presets role 2); every bulk (128-tile, LDS-DMA) launch polls
+        if (g.yield_role != 2) g.yield_role = gemm_f64_uses_dma(g) ? 1 : 0;
+    } else g.yield_role = 0;
     if (c->gemm_trace && gemm_f64_uses_dma128(g) && g.batch == 1) {
         const long mt = g.M / 128, nt = g.N / 128;
         const long nb = g.order ? g.norder : (g.tri == 2 ? mt * (mt + 1) / 2 : mt * nt);
@@ -687,481 +686,6 @@ int gemm_prof_pair(pgp_ctx* c, int cls_a, GemmArgs a, int cls_b, GemmArgs b, hip
       CHK(gemm_f64_launch(a, st)); }
     ProfScope ps(c, cls_b, b.flops, 0.0, st, gemm_f64_uses_dma128(b) ? PC_KERNEL_DMA128 : -1);
     return gemm_f64_launch(b, st);
-}
-
-// Blocked right-looking Cholesky of the (mrows x np) column-major lower matrix F (mrows >= np; rows
-// beyond np are "augmented" right-hand-side rows that receive the forward substitution for free).
-//
-// Two-level blocking: leaves of 128 columns (leaf_potrf -> trsm_rows -> inner update, K = 128) inside outer
-// panels of q leaves; the trailing matrix is updated once per outer panel with K = 128 q (C is read and
-// written once per 128 q columns: HBM arithmetic intensity 16 q flop/B).
-// Look-ahead (depth 1): the update of the NEXT panel's columns (TU_a) is issued first; the next panel is
-// then factored on the high-priority stream st2 while the rest of the trailing update (TU_b) runs on st.
-// rows_end(nb) = one past the last row that takes part once nb column blocks are factored
-struct RowEnd { long eoff; bool winv; long operator()(int nb) const { return winv ? eoff + (long)nb * 128 : eoff; } };
-
-// mark / mark_step: record `mark` on the stream after the mark_step-th kernel of the chain (1 = first leaf, 2 = its trsm,
-// 3 = its inner update, ...): the caller holds other work back until the chain has got that far
-static int factor_panel(pgp_ctx* c, double* F, long ld, RowEnd re, int s0, int s1, hipStream_t st,
-                        double* packs = nullptr, int info_base = 0, hipEvent_t mark = nullptr, int mark_step = 0) {
-    if (!packs) packs = c->inv16;
-    // the diagonal-panel chain of a look-ahead sweep (mark != null or a scratch factorisation next to bulk work): its kernels
-    // mark their CUs so that the bulk workgroups there give way
-    const bool chain = c->yield && c->yield_flags && packs == c->dpack;
-    unsigned* yfl = chain ? c->yield_flags : nullptr;
-    int step = 0;
-    auto stepped = [&]() -> int {
-        if (mark && ++step == mark_step) HIP_TRY(hipEventRecord(mark, st));
-        return PGP_OK;
-    };
-    if (mark && mark_step <= 0) HIP_TRY(hipEventRecord(mark, st));
-    for (int cb = s0; cb < s1; ++cb) {
-        double* Acc = F + (long)cb * 128 + (long)cb * 128 * ld;
-        double* pack = packs + (long)cb * PACK_DOUBLES;
-        {
-            ProfScope ps(c, PC_LEAF, 128.0 * 128.0 * 128.0 / 3.0, 0.0, st);
-            CHK(leaf_potrf_launch(Acc, ld, pack, c->info_dev, info_base + cb * 128, st, nullptr, yfl, c->leaf_pivot));
-        }
-        CHK(stepped());
-        const long rows_below = re(cb + 1) - (long)(cb + 1) * 128;
-        if (rows_below > 0) {
-            ProfScope ps(c, PC_TRSM, (double)rows_below * 128.0 * 128.0, 0.0, st);
-            CHK(trsm_rows_launch(Acc + 128, ld, rows_below, Acc, ld, pack, st, yfl, c->trsm_lean == 2 || (c->trsm_lean == 1 && chain)));
-        }
-        CHK(stepped());
-        if (cb + 1 < s1) {               // inner update of the rest of this outer panel, K = 128
-            GemmArgs g{};
-            g.A = Acc + 128; g.lda = ld; g.a_kc = 0;
-            g.B = Acc + 128; g.ldb = ld; g.b_kc = 0;
-            g.C = F + (long)(cb + 1) * 128 + (long)(cb + 1) * 128 * ld; g.ldc = ld;
-            g.M = (int)rows_below; g.N = (s1 - 1 - cb) * 128; g.K = 128;
-            g.alpha = -1.0; g.beta = 1.0; g.tri = 1; g.tri_off = 0; g.mask_diag = 1; g.kmode = KM_FULL;
-            const long t128 = (long)(g.M / 128) * (g.N / 128);
-            g.tile = t128 < c->small_tile_below ? 64 : 128;
-            g.flops = 2.0 * 128.0 * ((double)g.M * g.N - 0.5 * (double)g.N * g.N);
-            c->chain_now = chain ? 1 : 0;
-            const int rc_u = gemm_prof(c, PC_GEMM_INNER, g, st);
-            c->chain_now = 0;
-            CHK(rc_u);
-        }
-        CHK(stepped());
-    }
-    if (mark && step < mark_step) HIP_TRY(hipEventRecord(mark, st));      // a chain shorter than mark_step
-    return PGP_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// Cholesky sweep ("diagonal-panel" schedule).
-//
-// Only the w x w DIAGONAL block of an outer panel (w = 128 q = 512) goes through the leaf-level factorisation, in a small
-// scratch with identity rows appended so that E_D = L_D^-T falls out with it (diag_factor: D(p), a chain of 13 small
-// launches: stage in | 4 x [leaf_potrf, trsm_rows, K = 128 update] | stage out).  Everything below the block is then ONE MFMA GEMM per panel
-//        Y = X E_D        (solve_below: S(p);  K clipped to the triangle, k < j0 + T)
-// and the trailing update TU(p) is one K = w product.  Depth-1 look-ahead on two streams:
-//
-//   main :  S(p) -> TU_a(p) [next panel's columns, written to the staging buffer Xs] -> TU_b(p) [rest, in place] -> ...
-//   panel:                       D(p+1) (reads its diagonal block from Xs)  ..................^ joined before S(p+1)
-//
-// S is out of place (reads Xs, writes the factor / inverse rows), which is free: TU_a already reads and writes those
-// columns once, it just writes them to Xs instead.  The matrix lives in two pieces: logical rows [0, mrows) in F
-// (factor + rhs rows, what a posterior handle keeps) and rows [mrows, mrows + np) in E (fused inverse, scratch): with
-// the inverse rows riding through the sweep like the augmented right-hand-side rows, E <- E L^-T = L^-T = W^T.  Row i of
-// E stays zero left of its own column block, so after nb factored column blocks only the first 128 nb rows of E take part:
-// the extra work is N^3/3 flops -- exactly a triangular inverse -- inside the big K = w trailing-update launches.
-// dense2 > 0: the second piece is NOT the fused inverse but dense2 extra right-hand-side rows (all of them take part from
-// the first panel on: they receive the forward substitution X <- X L^-T, like the rhs rows inside F)
-struct SweepMat { double* F; long ldf; long mrows; double* E; long lde; long np; long dense2 = 0;
-                  long rows2(int blocks) const { return !E ? 0 : (dense2 > 0 ? dense2 : (long)blocks * 128); } };
-
-static int ensure_stage(pgp_ctx* c, long rows, int w) {
-    const size_t need = (size_t)rows * w * sizeof(double);
-    if (c->Xs_bytes >= need) return PGP_OK;
-    (void)hipStreamSynchronize(c->st);
-    if (c->Xs) (void)hipFree(c->Xs);
-    c->Xs = nullptr; c->Xs_bytes = 0;
-    HIP_TRY(hipMalloc((void**)&c->Xs, need));
-    c->Xs_bytes = need;
-    return PGP_OK;
-}
-
-// D: factor the w x w block `src` (leading dimension lds, lower part) and produce E_D = L_D^-T beside it: L_D -> Fd (ldf),
-// E_D -> Ed (lde; may be null), E_D also stays in c->Dk + w (leading dimension 2w) for the panel solve that follows
-// Dk: the 2w x w scratch (null: c->Dk); skip_out: the stage-out is left to the caller (diag_block_out, possibly on another stream)
-static int diag_block_factor_in(pgp_ctx* c, const double* src, long lds, int w, int info_base, hipStream_t st, hipEvent_t staged,
-                                double* Dk) {
-    const long ldd = 2L * w;
-    { ProfScope ps(c, PC_DIAG, 0.0, 8.0 * 3.0 * w * w, st);
-      CHK(diag_in_launch(src, lds, Dk, ldd, w, st)); }
-    return factor_panel(c, Dk, ldd, RowEnd{(long)w, true}, 0, w / 128, st, c->dpack, info_base, staged, c->leaf_first - 1);
-}
-static int diag_block_out(pgp_ctx* c, int w, double* Fd, long ldf, double* Ed, long lde, hipStream_t st, const double* Dk) {
-    ProfScope ps(c, PC_DIAG, 0.0, 8.0 * 3.0 * w * w, st);
-    return diag_out_launch(Dk, 2L * w, w, Fd, ldf, Ed, lde, st);
-}
-int diag_block_factor(pgp_ctx* c, const double* src, long lds, int w, double* Fd, long ldf, double* Ed, long lde,
-                      int info_base, hipStream_t st, hipEvent_t staged) {
-    CHK(diag_block_factor_in(c, src, lds, w, info_base, st, staged, c->Dk));
-    return diag_block_out(c, w, Fd, ldf, Ed, lde, st, c->Dk);
-}
-
-// D(p): the diagonal block of columns [s0, s1) (block units), src = its (updated) image with leading dim lds
-static int diag_factor(pgp_ctx* c, const SweepMat& m, int s0, int s1, const double* src, long lds, hipStream_t st,
-                       hipEvent_t staged = nullptr) {
-    return diag_block_factor(c, src, lds, (s1 - s0) * 128, m.F + (long)s0 * 128 * (1 + m.ldf), m.ldf,
-                             (m.E && !m.dense2) ? m.E + (long)s0 * 128 * (1 + m.lde) : nullptr, m.lde, s0 * 128, st, staged);
-}
-// D(p) in two halves (s_pan_out): stage-in + leaf chain in the scratch Dk, and -- later, on a stream of the caller's choice -- the stage-out
-static int diag_factor_in(pgp_ctx* c, const SweepMat& m, int s0, int s1, const double* src, long lds, hipStream_t st, double* Dk) {
-    return diag_block_factor_in(c, src, lds, (s1 - s0) * 128, s0 * 128, st, nullptr, Dk);
-}
-static int diag_factor_out(pgp_ctx* c, const SweepMat& m, int s0, int s1, hipStream_t st, const double* Dk) {
-    return diag_block_out(c, (s1 - s0) * 128, m.F + (long)s0 * 128 * (1 + m.ldf), m.ldf,
-                          (m.E && !m.dense2) ? m.E + (long)s0 * 128 * (1 + m.lde) : nullptr, m.lde, st, Dk);
-}
-
-// S(p): rows below the diagonal block of panel [s0, s1):  Y = X E_D, X read from the staging buffer (logical rows, ldx)
-static int solve_below(pgp_ctx* c, const SweepMat& m, int s0, int s1, const double* Xs, long ldx, hipStream_t st,
-                       const double* Dk = nullptr) {
-    const int w = (s1 - s0) * 128;
-    const long r0 = (long)s1 * 128, r1 = m.mrows + m.rows2(s0);
-    if (r1 <= r0) return PGP_OK;
-    GemmArgs g{};
-    g.A = Xs + r0; g.lda = ldx; g.a_kc = 0;
-    g.B = (Dk ? Dk : c->Dk) + w; g.ldb = 2L * w; g.b_kc = 1;  // B(n,k) = E_D(k,n): K-contiguous
-    g.C = m.F + r0 + (long)s0 * 128 * m.ldf; g.ldc = m.ldf;
-    if (m.E && r1 > m.mrows) { g.C2 = m.E + (long)s0 * 128 * m.lde; g.ldc2 = m.lde; g.c_split = (int)(m.mrows - r0); }
-    g.M = (int)(r1 - r0); g.N = w; g.K = w; g.alpha = 1.0; g.beta = 0.0;
-    g.kmode = KM_LT_J; g.koff = 0;
-    const long t128 = (long)(g.M / 128) * (w / 128);
-    // fewer 128-tiles than workgroup slots: the launch lasts as long as its longest (k = w) tile while the short-k tiles'
-    // CUs idle -- 64-tiles, long-k columns first, balance it (option s_tile: 0 = this rule, 64 / 128 = forced)
-    g.tile = c->s_tile ? c->s_tile : ((t128 < c->small_tile_below || t128 < 512) ? 64 : 128);
-    g.rev_cols = 1;
-    const double nt = (double)(w / g.tile);
-    g.flops = 2.0 * (double)g.M * g.tile * g.tile * nt * (nt + 1.0) * 0.5;
-    return gemm_prof(c, PC_GEMM_SOLVE, g, st);
-}
-
-// Option skip_zeros: the panel's own inverse rows (rows >= g.zero_from) hold E_D = L_D^-T, upper triangular, so tile row r of them
-// starts at k = T r (GemmArgs::zf_upper; T = the tile's rows) instead of multiplying the zeros left of the diagonal -- eet_panel_args
-// clips the same structure with KM_GE_I.  g.flops stays what is EXECUTED: the skipped products come off.
-static void trailing_skip(pgp_ctx* c, GemmArgs& g) {
-    if (!c->skip_zeros || g.zero_from <= 0 || g.zero_from >= g.M) return;
-    const int T = g.tile == 64 ? 64 : 128;
-    g.zf_upper = 1;
-    const double nr = (double)((g.M - g.zero_from) / T);
-    g.flops -= (double)T * T * g.N * nr * (nr - 1.0);                // sum_r 2 T N (T r)
-}
-
-// TU: C[rows >= c0, cols c0..c1) -= P P^T, P = solved columns [k0, k1); out != nullptr: result goes to the staging buffer
-static GemmArgs trailing_update2_args(pgp_ctx* c, const SweepMat& m, int k0, int k1, int c0, int c1, double* out, long ldx) {
-    const long r0 = (long)c0 * 128, r1 = m.mrows + m.rows2(k1);
-    GemmArgs g{};
-    g.A = m.F + r0 + (long)k0 * 128 * m.ldf; g.lda = m.ldf; g.a_kc = 0;
-    g.B = g.A; g.ldb = m.ldf; g.b_kc = 0;
-    double* Cf = m.F + r0 + (long)c0 * 128 * m.ldf;
-    const bool split = m.E && r1 > m.mrows;
-    const int sp = (int)(m.mrows - r0);
-    double* Ce = split ? m.E + (long)c0 * 128 * m.lde : nullptr;
-    if (split) { g.A2 = m.E + (long)k0 * 128 * m.lde; g.lda2 = m.lde; g.a_split = sp; }
-    if (out) {
-        g.Cin = Cf; g.ldcin = m.ldf; g.Cin2 = Ce; g.ldcin2 = m.lde;
-        g.C = out + r0; g.ldc = ldx;
-        if (split) { g.C2 = out + r0 + sp; g.ldc2 = ldx; g.c_split = sp; }
-    } else {
-        g.C = Cf; g.ldc = m.ldf;
-        if (split) { g.C2 = Ce; g.ldc2 = m.lde; g.c_split = sp; }
-    }
-    g.M = (int)(r1 - r0); g.N = (c1 - c0) * 128; g.K = (k1 - k0) * 128;
-    g.alpha = -1.0; g.beta = 1.0; g.tri = 1; g.tri_off = 0; g.mask_diag = 1; g.kmode = KM_FULL;
-    if (split && !m.dense2) g.zero_from = (int)(m.mrows + (long)k0 * 128 - r0);     // this panel's own inverse rows: first touch
-    const long t128 = (long)(g.M / 128) * (g.N / 128) - (long)(g.N / 128) * (g.N / 128 - 1) / 2;
-    g.tile = t128 < c->small_tile_below ? 64 : 128;
-    g.flops = 2.0 * (double)g.K * ((double)g.M * g.N - 0.5 * (double)g.N * g.N);
-    trailing_skip(c, g);
-    return g;
-}
-// TU_a in two pieces (sched 2): columns [c0, c1) <- C - P P^T restricted to the row blocks [rb0, rb1) (rb1 < 0: to the last row
-// that takes part).  rb0 == c0, rb1 == c1: the DIAGONAL BLOCK of the next panel alone (lower-triangular tile set) -- all D(p+1)
-// needs; rb0 == c1: the rectangle below it.  Results go to the staging buffer like TU_a's.
-static GemmArgs trailing_update_rows_args(pgp_ctx* c, const SweepMat& m, int k0, int k1, int rb0, int rb1, int c0, int c1,
-                                          double* out, long ldx, int tile) {
-    const long r0 = (long)rb0 * 128, rend = m.mrows + m.rows2(k1);
-    const long r1 = rb1 >= 0 ? (long)rb1 * 128 : rend;
-    GemmArgs g{};
-    g.A = m.F + r0 + (long)k0 * 128 * m.ldf; g.lda = m.ldf; g.a_kc = 0;
-    g.B = m.F + (long)c0 * 128 + (long)k0 * 128 * m.ldf; g.ldb = m.ldf; g.b_kc = 0;
-    double* Cf = m.F + r0 + (long)c0 * 128 * m.ldf;
-    const bool split = m.E && r1 > m.mrows;
-    const int sp = (int)(m.mrows - r0);
-    double* Ce = split ? m.E + (long)c0 * 128 * m.lde : nullptr;
-    if (split) { g.A2 = m.E + (long)k0 * 128 * m.lde; g.lda2 = m.lde; g.a_split = sp; }
-    g.Cin = Cf; g.ldcin = m.ldf; g.Cin2 = Ce; g.ldcin2 = m.lde;
-    g.C = out + r0; g.ldc = ldx;
-    if (split) { g.C2 = out + r0 + sp; g.ldc2 = ldx; g.c_split = sp; }
-    g.M = (int)(r1 - r0); g.N = (c1 - c0) * 128; g.K = (k1 - k0) * 128;
-    g.alpha = -1.0; g.beta = 1.0; g.kmode = KM_FULL;
-    if (rb0 == c0) { g.tri = 1; g.tri_off = 0; g.mask_diag = 1; }
-    if (split && !m.dense2) g.zero_from = (int)(m.mrows + (long)k0 * 128 - r0);
-    g.tile = tile;
-    g.flops = 2.0 * (double)g.K * ((double)g.M * g.N - (rb0 == c0 ? 0.5 * (double)g.N * g.N : 0.0));
-    trailing_skip(c, g);
-    return g;
-}
-
-static int trailing_update2(pgp_ctx* c, const SweepMat& m, int k0, int k1, int c0, int c1, double* out, long ldx,
-                            hipStream_t st) {
-    if (c1 <= c0) return PGP_OK;
-    return gemm_prof(c, PC_GEMM_TRAIL, trailing_update2_args(c, m, k0, k1, c0, c1, out, ldx), st);
-}
-
-// Filler: B^-1 (lower) += E_p E_p^T with E_p = columns [s0, s1) of E = L^-T, which are FINAL once S(p) has run (right-
-// looking sweep).  E_p is non-zero in rows < 128 s1 only, so the product covers the leading 128 s1 square; its rows
-// >= 128 s0 are touched for the first time (zero_from), and inside the diagonal block k starts at the row (KM_GE_I).
-static GemmArgs eet_panel_args(pgp_ctx* c, const SweepMat& m, int s0, int s1, double* Binv, long ldb) {
-    GemmArgs g{};
-    g.A = m.E + (long)s0 * 128 * m.lde; g.lda = m.lde; g.a_kc = 0;
-    g.B = g.A; g.ldb = m.lde; g.b_kc = 0;
-    g.C = Binv; g.ldc = ldb;
-    g.M = s1 * 128; g.N = s1 * 128; g.K = (s1 - s0) * 128; g.alpha = 1.0; g.beta = s0 > 0 ? 1.0 : 0.0;
-    g.tri = 2; g.mask_diag = 1; g.kmode = KM_GE_I; g.koff = -s0 * 128;
-    if (s0 > 0) g.zero_from = s0 * 128;
-    const long t128 = (long)s1 * (s1 + 1) / 2;
-    g.tile = (t128 < c->small_tile_below || c->eet_tile == 64) ? 64 : 128;
-    const double w = (double)g.K, r0 = 128.0 * s0;
-    g.flops = w * r0 * r0 + w * w * r0 + w * w * w / 3.0;      // old x old (lower) + new x old (k >= row) + new x new
-    return g;
-}
-static int eet_panel(pgp_ctx* c, const SweepMat& m, int s0, int s1, double* Binv, long ldb, hipStream_t st) {
-    return gemm_prof(c, PC_GEMM_LAUUM, eet_panel_args(c, m, s0, s1, Binv, ldb), st);
-}
-
-static int potrf_blocked_v2(pgp_ctx* c, const SweepMat& m) {
-    const int nblk = (int)(m.np / 128);
-    // panel width: 512 columns; 1024 from N = 12288 on (measured: the K = 1024 updates and the halved number of chain
-    // steps win 1.4 % at N = 12288, 1.6 % at 16384, 3 % at 20480; at N = 8192 the 512-wide panels win by 4 %)
-    const int q = c->nb_outer > 0 ? std::min(c->nb_outer, 8) : (nblk >= 96 ? 8 : 4);
-    const int npanel = (nblk + q - 1) / q;
-    const int wmax = q * 128;
-    const long ldx = m.mrows + (m.dense2 > 0 ? m.dense2 : m.np);   // staging buffer indexed by logical row
-    const bool la = c->lookahead && npanel >= 3;
-    CHK(ensure_stage(c, ldx, wmax));
-    double* Xs = c->Xs;
-    if (la)
-        while ((int)c->la_ev.size() < 2 * npanel + 2) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            c->la_ev.push_back(e);
-        }
-    hipStream_t main = c->st, pan = la ? c->st2 : c->st;
-    // panel 0: its columns go to the staging buffer by a plain copy (later panels get there through TU_a)
-    {
-        const int s1 = std::min(q, nblk);
-        const long r0 = (long)s1 * 128;
-        if (m.mrows > r0)
-            HIP_TRY(hipMemcpy2DAsync(Xs + r0, ldx * sizeof(double), m.F + r0, m.ldf * sizeof(double),
-                                     (m.mrows - r0) * sizeof(double), (size_t)s1 * 128, hipMemcpyDeviceToDevice, main));
-        if (m.E && m.dense2 > 0)                                  // the dense second piece takes part from panel 0 on
-            HIP_TRY(hipMemcpy2DAsync(Xs + m.mrows, ldx * sizeof(double), m.E, m.lde * sizeof(double),
-                                     m.dense2 * sizeof(double), (size_t)s1 * 128, hipMemcpyDeviceToDevice, main));
-        CHK(diag_factor(c, m, 0, s1, m.F, m.ldf, main));
-    }
-    c->eet_join = nullptr;
-    // B^-1 = sum_p E_p E_p^T accumulated under the sweep (eet_overlap 2, or 3 up to eet_max_panels panels: beyond that the
-    // chain is amortised and the one-shot long-K product is faster): panel p's share right behind TU_b(p) on the main
-    // stream -- the main stream stays busy until D(p+1) is done instead of waiting for it
-    const bool fill_inline = la && m.E && !m.dense2 && c->eet_out &&
-                             (c->eet_overlap == 2 || (c->eet_overlap == 3 && npanel <= c->eet_max_panels));
-    // dense right-hand-side rows R (EP: R L^-T = V' = K sW L^-T): the caller's symmetric C -= V' V'^T is accumulated panel by
-    // panel behind TU_b as well -- at N = 4096 the sweep is bound by the chain of diagonal blocks and the main stream would
-    // wait for D(p+1) anyway
-    const bool fill2 = m.dense2 > 0 && c->fill2_C != nullptr;
-    auto rhs_product = [&](int s0, int s1) -> int {
-        GemmArgs g{};
-        g.A = m.E + (long)s0 * 128 * m.lde; g.lda = m.lde; g.a_kc = 0;
-        g.B = g.A; g.ldb = m.lde; g.b_kc = 0;
-        g.C = c->fill2_C; g.ldc = c->fill2_ld; g.M = (int)m.dense2; g.N = (int)m.dense2; g.K = (s1 - s0) * 128;
-        g.alpha = -1.0; g.beta = 1.0; g.tile = 128; g.tri = 2; g.mask_diag = 1;
-        g.flops = (double)m.dense2 * m.dense2 * g.K;
-        return gemm_prof(c, PC_GEMM_INNER, g, main);
-    };
-    // sched 1 (round 5): the CRITICAL PATH  D(p) -> S(p) -> TU_a(p) -> D(p+1)  lives on the (high-priority) panel stream, the bulk --
-    // TU_b(p) + E E'(p) -- on the main stream.  The two under-filled launches of a panel (S: ~250 tile units, TU_a: ~230) then run
-    // BESIDE the previous panel's bulk launch and its tail instead of alone on the chip between two bulk launches, and D(p+1) starts
-    // without waiting for them to drain a full chip.  Events: main waits for S(p) before TU_b(p); the panel stream waits for
-    // TU_b(p-1) (which brought panel p+1's columns up to date) before TU_a(p).  Same kernels, same per-tile order: bit-identical.
-    // sched 1 is what fit streams that run side by side ask for (_lib.concurrent_fit_streams); it pays from N ~ 7000 on (two streams,
-    // N = 8192: 109.5 vs 107.7 fits/s with sched 2) and costs below (N = 6144: 218.5 vs 225.3; N = 4096: 467 vs 513 / 521 with
-    // sched 2 / 0): smaller sweeps take the default schedule instead
-    const int sched_req = (c->concurrent_streams && !c->sched_explicit) ? 1 : c->sched;     // fit streams side by side: sched 1 unless the user chose
-    const int sched_eff = (sched_req == 1 && nblk < 56) ? PGP_SCHED_DEFAULT : sched_req;
-    const bool sched1 = la && sched_eff == 1 && !m.dense2;
-    // sched 2 pays for 512-wide panels only (N = 4096: -3.6 %, N = 8192: -2.1 %); with 1024-wide panels the diagonal-block piece is
-    // 136 K = 1024 tiles and the rectangle it disturbs twice as long: N = 16384 68.9 -> 70.3 ... 71.2 ms -- those keep schedule 0
-    // ... and only with the fused inverse rows in the sweep: a plain factorisation (jitchol, EP's post.L) is bound by the chain on a
-    // mostly idle chip, where the extra event and the marked piece only add to it (EP's final factor with 512-wide panels: 17.5 ->
-    // 18.0 ms per fit with sched 2)
-    // ... and from N = 4096 on (measured: N = 2048 1.267 -> 1.313 ms, N = 4096 2.94 -> 2.88, N = 8192 11.13 -> 10.90)
-    const bool sched2 = la && sched_eff == 2 && !m.dense2 && m.E != nullptr && ((q <= 4 && nblk >= 32 && nblk < 72) || c->sched2_wide);     // N = 6144: 6.08 -> 5.78 ms; N = 10240: 19.67 -> 19.76
-    const bool span = sched2 && !c->leaf_first && c->s_pan != 0;
-    // the stage-out of D(p) off the chain; the scratch is double-buffered by panel parity (2w x w doubles each, w <= 512: the two
-    // halves of c->Dk), so that D(p+1) may stage in while S(p) / the stage-out of D(p) still read D(p)'s
-    const bool span_out = span && c->s_pan_out && q <= 4;
-    auto Dkp = [&](int p) -> double* { return span_out ? c->Dk + (size_t)(p & 1) * 1024 * 1024 : c->Dk; };
-    if (span)
-        while ((int)c->la_ev.size() < 5 * npanel + 5) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            c->la_ev.push_back(e);
-        }
-    if (sched1) {
-        while ((int)c->la_ev.size() < 2 * npanel + 4) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            c->la_ev.push_back(e);
-        }
-        auto EV_S = [&](int p) { return c->la_ev[2 * p]; };           // S(p) done (panel stream)
-        auto EV_B = [&](int p) { return c->la_ev[2 * p + 1]; };       // TU_b(p) [+ E E'(p)] done (main stream)
-        hipEvent_t ev0 = c->la_ev[2 * npanel + 2];
-        HIP_TRY(hipEventRecord(ev0, main));                           // panel 0's staging copy and D(0) ran on main
-        HIP_TRY(hipStreamWaitEvent(pan, ev0, 0));
-        const int pf = std::min(c->eet_first >= 0 ? c->eet_first : npanel / 6, npanel - 2);
-        for (int p = 0; p < npanel; ++p) {
-            const int s0 = p * q, s1 = std::min(s0 + q, nblk);
-            CHK(solve_below(c, m, s0, s1, Xs, ldx, pan));
-            HIP_TRY(hipEventRecord(EV_S(p), pan));
-            HIP_TRY(hipStreamWaitEvent(main, EV_S(p), 0));
-            if (s1 >= nblk) break;
-            const int n0 = s1, n1 = std::min(s1 + q, nblk);
-            if (p >= 1) HIP_TRY(hipStreamWaitEvent(pan, EV_B(p - 1), 0));
-            CHK(trailing_update2(c, m, s0, s1, n0, n1, Xs, ldx, pan));            // TU_a -> staging
-            CHK(diag_factor(c, m, n0, n1, Xs + (long)n0 * 128, ldx, pan));        // D(p+1)
-            const bool fill_now = fill_inline && p >= pf;
-            if (fill_now && n1 < nblk && c->pair_launch) {
-                CHK(gemm_prof_pair(c, PC_GEMM_TRAIL, trailing_update2_args(c, m, s0, s1, n1, nblk, nullptr, 0), PC_GEMM_LAUUM,
-                                   eet_panel_args(c, m, p == pf ? 0 : s0, s1, c->eet_out, c->eet_ld), main));
-            } else {
-                CHK(trailing_update2(c, m, s0, s1, n1, nblk, nullptr, 0, main));
-                if (fill_now) CHK(eet_panel(c, m, p == pf ? 0 : s0, s1, c->eet_out, c->eet_ld, main));
-            }
-            HIP_TRY(hipEventRecord(EV_B(p), main));
-        }
-    } else
-    for (int p = 0; p < npanel; ++p) {
-        const int s0 = p * q, s1 = std::min(s0 + q, nblk);
-        if (span_out && p >= 1) {
-            // s_pan_out: D(p)'s stage-out (L_D -> F, E_D -> E; S(p) reads E_D from the scratch) is off the chain: it runs on the main stream
-            // (which has waited for D(p)'s leaf chain) beside S(p), ahead of TU_r(p) -- the first reader of E_D's copy in E
-            CHK(diag_factor_out(c, m, s0, s1, main, Dkp(p)));
-        }
-        if (span && p >= 1) {
-            // s_pan: S(p) does not wait for the END of the paired launch of panel p - 1 (which D(p) beats by ~35 us): it follows
-            // D(p) on the panel stream and runs in that launch's tail.  It reads the staging rows TU_r(p-1) wrote (main stream)
-            HIP_TRY(hipStreamWaitEvent(pan, c->la_ev[2 * npanel + 2 + 2 * (p - 1)], 0));
-            const int was = c->chain_now;
-            c->chain_now = c->s_pan == 2 ? 1 : was;
-            const int rc = solve_below(c, m, s0, s1, Xs, ldx, pan, Dkp(p));
-            c->chain_now = was;
-            CHK(rc);
-            HIP_TRY(hipEventRecord(c->la_ev[2 * npanel + 3 + 2 * (p - 1)], pan));
-            HIP_TRY(hipStreamWaitEvent(main, c->la_ev[2 * npanel + 3 + 2 * (p - 1)], 0));
-        } else
-        CHK(solve_below(c, m, s0, s1, Xs, ldx, main));
-        if (fill2 && s1 >= nblk) CHK(rhs_product(s0, s1));
-        if (s1 >= nblk) break;
-        const int n0 = s1, n1 = std::min(s1 + q, nblk);              // next panel's columns
-        const long rows_end = m.mrows + m.rows2(s1);
-        if (sched2 && rows_end > (long)n1 * 128) {
-            // sched 2: D(p+1) needs the next panel's DIAGONAL BLOCK only -- that piece of TU_a (64-tiles: a K = w 128-tile alone
-            // on a CU lasts as long as the whole of TU_a) goes to the panel stream right behind S(p), the rectangle below it
-            // stays on the main stream: D(p+1) starts ~50 us earlier, and its first kernels find free slots beside the
-            // one-workgroup-per-CU rectangle instead of the first wave of the bulk launch
-            if (span && p >= 1 && c->s_pan_direct) {
-                // S(p) sits on the panel stream already: the piece only needs the paired launch of panel p - 1 (its event), not a
-                // round trip through the main stream's wait for S(p) (26 us between S(p) and the piece before)
-                HIP_TRY(hipStreamWaitEvent(pan, c->la_ev[4 * npanel + 4 + (p - 1)], 0));
-            } else {
-            HIP_TRY(hipEventRecord(c->la_ev[2 * p], main));
-            HIP_TRY(hipStreamWaitEvent(pan, c->la_ev[2 * p], 0));
-            }
-            {
-                const int was = c->chain_now;
-                c->chain_now = c->tud_mark ? 1 : was;
-                const int rc = gemm_prof(c, PC_GEMM_TRAIL, trailing_update_rows_args(c, m, s0, s1, n0, n1, n0, n1, Xs, ldx, c->tud_tile), pan);
-                c->chain_now = was;
-                CHK(rc);
-            }
-            CHK(gemm_prof(c, PC_GEMM_TRAIL, trailing_update_rows_args(c, m, s0, s1, n1, -1, n0, n1, Xs, ldx, c->tur_tile ? c->tur_tile : (nblk <= 40 ? 1264 : 128)), main));
-        } else {
-        CHK(trailing_update2(c, m, s0, s1, n0, n1, Xs, ldx, main));   // TU_a -> staging
-        if (la) {
-            HIP_TRY(hipEventRecord(c->la_ev[2 * p], main));
-            HIP_TRY(hipStreamWaitEvent(pan, c->la_ev[2 * p], 0));
-        }
-        }
-        if (span) HIP_TRY(hipEventRecord(c->la_ev[2 * npanel + 2 + 2 * p], main));     // TU_a(p)'s rows below the diagonal block are staged
-        // leaf_first: the trailing update is held back until D(p+1)'s stage-in is done, so that the first leaf is dispatched
-        // BEFORE the update's first wave takes every workgroup slot (a leaf dispatched into that wave waits ~140 us for it)
-        const bool lf = la && c->leaf_first;
-        if (span_out) CHK(diag_factor_in(c, m, n0, n1, Xs + (long)n0 * 128, ldx, pan, Dkp(p + 1)));
-        else
-        CHK(diag_factor(c, m, n0, n1, Xs + (long)n0 * 128, ldx, pan, lf ? c->la_ev[2 * npanel + (p & 1)] : nullptr));
-        if (lf) HIP_TRY(hipStreamWaitEvent(main, c->la_ev[2 * npanel + (p & 1)], 0));
-        if (la) HIP_TRY(hipEventRecord(c->la_ev[2 * p + 1], pan));
-        // the first products are small (few tiles, short k) and the early trailing updates are long enough to hide D by
-        // themselves: panels 0 .. eet_first go into ONE product (k = (eet_first + 1) w) behind TU_b(eet_first)
-        const int pf = std::min(c->eet_first >= 0 ? c->eet_first : npanel / 6, npanel - 2);
-        const bool fill_now = fill_inline && p >= pf;
-        if (fill_now && n1 < nblk && c->pair_launch) {
-            // TU_b(p) in place (concurrent with D(p+1)) and panel p's share of E E' are independent: ONE launch, one tail
-            CHK(gemm_prof_pair(c, PC_GEMM_TRAIL, trailing_update2_args(c, m, s0, s1, n1, nblk, nullptr, 0), PC_GEMM_LAUUM,
-                               eet_panel_args(c, m, p == pf ? 0 : s0, s1, c->eet_out, c->eet_ld), main));
-        } else {
-            CHK(trailing_update2(c, m, s0, s1, n1, nblk, nullptr, 0, main));   // TU_b in place, concurrent with D(p+1)
-            if (fill_now) CHK(eet_panel(c, m, p == pf ? 0 : s0, s1, c->eet_out, c->eet_ld, main));
-        }
-        if (fill2) CHK(rhs_product(s0, s1));
-        if (span) HIP_TRY(hipEventRecord(c->la_ev[4 * npanel + 4 + p], main));          // TU_b(p) [+ E E'(p)] queued: what TU_d(p+1) waits for
-        if (la) HIP_TRY(hipStreamWaitEvent(main, c->la_ev[2 * p + 1], 0));
-    }
-    if (fill_inline) {
-        // the last product has nothing of the sweep left to hide: it goes to the (now idle) panel stream so that the O(N^2)
-        // kernels that follow the sweep on the main stream (alpha = E z, log det) run beside it; the fit joins on eet_join
-        const int s0 = npanel >= 2 ? (npanel - 1) * q : 0;
-        while ((int)c->fill_ev.size() < 2) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            c->fill_ev.push_back(e);
-        }
-        HIP_TRY(hipEventRecord(c->fill_ev[0], main));
-        HIP_TRY(hipStreamWaitEvent(pan, c->fill_ev[0], 0));
-        CHK(eet_panel(c, m, s0, nblk, c->eet_out, c->eet_ld, pan));
-        HIP_TRY(hipEventRecord(c->fill_ev[1], pan));
-        c->eet_join = c->fill_ev[1];
-    }
-    return PGP_OK;
-}
-
-// Entry point.  with_inverse: the np rows [mrows, mrows + np) end up holding E = L^-T (upper triangular).  They live at
-// E (leading dimension lde) or, when E is null, directly below the factor's rows in the same buffer (F + mrows, ld).
-// The sweep writes EVERY entry of the inverse rows it later reads, so E needs no initialisation.
-int potrf_blocked(pgp_ctx* c, double* F, long ld, long np, long mrows, bool with_inverse, double* E, long lde) {
-    if (with_inverse && !E) { E = F + mrows; lde = ld; }
-    // two-piece row space: the panel solves / updates address "rows >= mrows" through a split that must be positive for
-    // every panel, i.e. at least one spare row block between the factor's rows and the inverse rows
-    if (with_inverse && E != F + mrows && mrows < np + 128) return -1;
-    SweepMat m{F, ld, mrows, with_inverse ? E : nullptr, lde, np};
-    return potrf_blocked_v2(c, m);
-}
-
-// The same sweep with a SECOND piece of nrhs2 dense right-hand-side rows in their own buffer R (leading dimension ldr; row n,
-// column k at R[n + k ldr]): on return R = R L^-T, i.e. row n of R holds (L^-1 r_n)' for the right-hand side r_n = R(n, :)'.
-// The rows ride along in the panel solves and trailing updates of the sweep (N^2 flops per row inside the bulk MFMA launches).
-int potrf_blocked_rhs(pgp_ctx* c, double* F, long ld, long np, long mrows, double* R, long ldr, long nrhs2) {
-    if (!R || nrhs2 <= 0 || nrhs2 % 128 || mrows < np + 128) return -1;
-    SweepMat m{F, ld, mrows, R, ldr, np};
-    m.dense2 = nrhs2;
-    return potrf_blocked_v2(c, m);
 }
 
 // W = L^-1 (column-major lower, np x np).  Level 0: batched inversion of the 128-blocks; then the
@@ -1489,10 +1013,9 @@ int pgp_exact_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para
     CHK(aug_rhs_launch(c->y_dev, c->m_dev, n, F, ldf, np, c->rvec, st));
     // ---- S2: Cholesky (forward substitution of the augmented row -- and L^-T -- ride along) ----------
     HIP_TRY(hipEventRecord(c->ev[1], st));
-    if (fused && want >= 3) { c->eet_out = c->Binv; c->eet_ld = np; }
-    c->eet_join = nullptr;
-    const int prc = potrf_blocked(c, F, ldf, np, np + 128, fused, E, lde);
-    c->eet_out = nullptr;
+    SweepJob job{F, ldf, np, np + 128, fused, E, lde};
+    if (fused && want >= 3) { job.eet_out = c->Binv; job.eet_ld = np; }
+    const int prc = potrf_blocked(c, job);
     if (prc != PGP_OK) (void)hipDeviceSynchronize();                              // queued products still read the scratch E
     CHK(prc);
     HIP_TRY(hipEventRecord(c->ev[2], st));
@@ -1519,7 +1042,7 @@ int pgp_exact_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para
     HIP_TRY(hipEventRecord(c->ev[4], st));
     // ---- S5b: B^-1 = W^T W ; S6: gradient reduce ------------------------------------------------
     if (want >= 3) {
-        if (fused && c->eet_join) HIP_TRY(hipStreamWaitEvent(st, c->eet_join, 0));        // accumulated under the sweep
+        if (fused && job.join) HIP_TRY(hipStreamWaitEvent(st, job.join, 0));        // accumulated under the sweep
         else if (fused) CHK(eet_lower(c, E, lde, c->Binv, np, np));                   // B^-1 = W^T W = E E^T
         else CHK(lauum_lower(c, c->W, np, c->Binv, np, np));
         HIP_TRY(hipEventRecord(c->ev[5], st));
@@ -1721,7 +1244,8 @@ int pgp_potrf(pgp_ctx* c, const double* A, int64_t n, double* L_out) {
     HIP_TRY(hipMemsetAsync(c->info_dev, 0, sizeof(int), st));
     double* pack_save = c->inv16;                  // the blocked driver takes the per-leaf operand images from the ctx
     c->inv16 = pack;
-    const int rc = potrf_blocked(c, F, np, np, np);
+    SweepJob job{F, np, np, np};
+    const int rc = potrf_blocked(c, job);
     c->inv16 = pack_save;
     CHK(rc);
     int info = 0;

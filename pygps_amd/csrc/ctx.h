@@ -1,4 +1,4 @@
-// Internal: context / factor structs shared by the host-side drivers (capi.hip, predict.hip, ep.hip).
+// Internal: context / factor structs shared by the host-side drivers (capi.hip, sweep.hip, predict.hip, ep.hip).
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -6,7 +6,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <map>
-#include <mutex>
 #include <mutex>
 #include <vector>
 
@@ -50,19 +49,14 @@ struct pgp_ctx {
     std::vector<int> composite;         // postfix program of kind PGP_COV_COMPOSITE (pgp_set_composite)
     hipStream_t st = nullptr;
     hipStream_t st2 = nullptr;          // panel stream of the look-ahead Cholesky (high priority)
-    std::vector<hipEvent_t> fill_ev;
+    std::vector<hipEvent_t> fill_ev;    // Cholesky sweep: the two events around the last E E^T product on the panel stream
     std::vector<hipEvent_t> ep_ev;      // EP block sweep: the two events around a sweep (bulk stream -> chain stream and back)
-    double* eet_out = nullptr;          // set by the fit for the duration of one sweep: where the filler accumulates B^-1
-    long eet_ld = 0;
-    double* fill2_C = nullptr;          // potrf_blocked_rhs: symmetric matrix (lower tiles) that receives -= V' V'^T panel by panel, or null
-    long fill2_ld = 0;
-    hipEvent_t eet_join = nullptr;      // non-null: the sweep queued every panel product; the fit joins on this event
     int eet_tile = 128;                 // tile size of the filler products (64: shorter workgroups in the way of the chain)
     int eet_first = -1;                 // inline filler: panels 0 .. eet_first are folded into one product (-1: a sixth of the panels)
     int eet_overlap = 3;                // B^-1 = sum_p E_p E_p^T accumulated under the sweep: 0 off (one product after it), 2 behind
                                         // every TU_b on the main stream, 3 the same when npanel <= eet_max_panels
     int eet_max_panels = 32;
-    std::vector<hipEvent_t> la_ev;      // look-ahead hand-off events
+    std::vector<hipEvent_t> la_ev;      // look-ahead hand-off events (sweep.hip SweepEvents; the sharded fit lays its own map over them)
     std::vector<hipEvent_t> tm_ev;      // timing events of the sharded fit's wait / broadcast timers (4 per panel)
     int lookahead = 1;
     bool sched_explicit = false;        // "sched" was set to a value >= 0 by the caller: the concurrent-streams hint does not override it
@@ -71,7 +65,7 @@ struct pgp_ctx {
                                         // panel stream; 1 = the critical path D -> S -> TU_a on the panel stream, the bulk updates on the main
                                         // stream (what fit streams that run side by side select); 2 = like 0, but the piece of TU_a that D(p+1)
                                         // needs -- the next panel's diagonal block -- runs on the panel stream right behind S(p)
-                                        // (potrf_blocked_v2; lone chain at N = 8192: 11.13 -> 10.90 ms)
+                                        // (sweep.hip; lone chain at N = 8192: 11.13 -> 10.90 ms)
     int tur_tile = 0;                   // sched 2: tiles of the rectangle below it (TU_r, main stream): 128, or 1264 = 128 x 64 LDS-DMA tiles (two workgroups per
                                         // CU: 78 -> 70 us alone on the chip at N = 8192); 0 = by size: 1264 up to N = 5120 (N = 4096: two streams +2 ... 3 %,
                                         // single chain equal), 128 beyond (N = 8192: the chain's kernels find no free slot beside two workgroups per CU:
@@ -100,7 +94,6 @@ struct pgp_ctx {
     long gemm_trace_cap = 0;            // clock (GemmArgs::trace), one behind the other, until v * 1024 workgroups are recorded --
     long gemm_trace_pos = 0;            // pgp_test_read_gemm_trace reads and rewinds; 0 frees the buffer
     unsigned* yield_flags = nullptr;    // the device's per-CU table (shared by every context on the device)
-    int chain_now = 0;                  // set by the sweep while it queues the chain's kernels (factor_panel)
     int ep_fused = 2;                   // EP parameter recomputation: 0 blocked multi-rhs solve, 1 through the fused inverse (V' = K diag(sW)
                                         // L^-T as one product), 2 K diag(sW) as dense right-hand-side rows of the sweep
     int ep_r_direct = 1;                // EP gradient: sW sW' o B^-1 = S - S Sigma S from the rebuilt Sigma; 0 = triangular inverse + W'W
@@ -395,8 +388,23 @@ void prof_collect(pgp_ctx* c);
 static inline long round_up(long v, long m) { return (v + m - 1) / m * m; }
 int make_spec(pgp_ctx* c, int kind, const double* hyp, int nhyp, int para, int flags, int der, long d, CovSpec& cs);
 int cov_point_value(pgp_ctx* c, const CovSpec& cs, int train, double* out);
-int potrf_blocked(pgp_ctx* c, double* F, long ld, long np, long mrows, bool with_inverse = false, double* E = nullptr,
-                  long lde = 0);
+// One Cholesky sweep (sweep.hip): the (mrows x np) column-major lower matrix F (mrows >= np; the rows beyond np are right-hand-side
+// rows that receive the forward substitution) and an optional second piece of rows in a buffer of its own.
+struct SweepJob {
+    double* F; long ldf, np, mrows;               // factor (+ augmented rows)
+    bool inverse = false;                         // the np fused inverse rows E = L^-T ride along; they need no initialisation
+    double* E = nullptr; long lde = 0;            // ... here, or (null) directly below the factor's rows: F + mrows, ldf
+    double* R = nullptr; long ldr = 0, nrhs2 = 0; // dense right-hand-side rows (instead of E): on return R = R L^-T
+    double* eet_out = nullptr; long eet_ld = 0;   // B^-1 += E_p E_p^T under the sweep, or null
+    double* rhs_C = nullptr;  long rhs_ld = 0;    // C -= R_p R_p^T under the sweep (symmetric, lower tiles), or null
+    hipEvent_t join = nullptr;                    // OUT: non-null when the last product went to the panel stream: the caller joins on it
+};
+int potrf_blocked(pgp_ctx* c, SweepJob& job);
+// grow-only pools of untimed events (la_ev, fill_ev, ep_ev)
+static inline int ensure_events(std::vector<hipEvent_t>& ev, size_t n) {
+    for (hipEvent_t e; ev.size() < n; ev.push_back(e)) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return PGP_OK;
+}
 int gemm_prof(pgp_ctx* c, int cls, GemmArgs g, hipStream_t st = nullptr);
 int gemm_prof_pair(pgp_ctx* c, int cls_a, GemmArgs a, int cls_b, GemmArgs b, hipStream_t st = nullptr);
 int batch_tile_list(pgp_ctx* c, int mt0, int nt, int nb, int dmt, const int** out, int* n);
@@ -453,7 +461,6 @@ int alloc_factor_buffer(pgp_ctx* c, long np, long ldf, double** F);
 int ensure_workspace(pgp_ctx* c, long np);
 int solve_lower_multi(pgp_ctx* c, const double* L, long ldl, const double* Wd, double* Y, long ldy, long np, int nrhs,
                       bool trans);
-int potrf_blocked_rhs(pgp_ctx* c, double* F, long ld, long np, long mrows, double* R, long ldr, long nrhs2);
 int eet_lower(pgp_ctx* c, const double* E, long lde, double* Binv, long ldb, long np);
 
 // ---- GPMC (gpmc.hip): one-vs-one pairs on one shared covariance matrix ----------------------------------------------------

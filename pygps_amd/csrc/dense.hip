@@ -112,17 +112,16 @@ int pgp_exact_fit_dense(pgp_ctx* c, const double* K, int64_t n, const double* r,
     hipLaunchKernelGGL(dense_to_factor_kernel, dim3((unsigned)((np + 255) / 256), (unsigned)std::min<long>(np, 65535)), dim3(256), 0, st, Kd, n, 1.0 / sn2, F,
                        ldf, np);
     CHK(aug_rhs_launch(c->zvec, zero, n, F, ldf, np, c->rvec, st));
-    if (fused) { c->eet_out = c->Binv; c->eet_ld = np; }
-    c->eet_join = nullptr;
-    const int prc = potrf_blocked(c, F, ldf, np, np + 128, fused, E, np);
-    c->eet_out = nullptr;
+    SweepJob job{F, ldf, np, np + 128, fused, E, np};
+    if (fused) { job.eet_out = c->Binv; job.eet_ld = np; }
+    const int prc = potrf_blocked(c, job);
     if (prc != PGP_OK) (void)hipDeviceSynchronize();
     CHK(prc);
     CHK(logdet_ztz_launch(F, ldf, n, F + np, ldf, c->scal, st));
     CHK(gather_strided_launch(F + np, ldf, np, c->zvec, st));
     if (fused) {
         CHK(upper_matvec_launch(E, np, np, c->zvec, 1.0 / sn2, c->partial, c->alpha_dev, st));
-        if (c->eet_join) HIP_TRY(hipStreamWaitEvent(st, c->eet_join, 0));
+        if (job.join) HIP_TRY(hipStreamWaitEvent(st, job.join, 0));
         else CHK(eet_lower(c, E, np, c->Binv, np, np));
         hipLaunchKernelGGL(dense_trace_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c->Binv, np, c->alpha_dev, n, sn2,
                            c->partial);

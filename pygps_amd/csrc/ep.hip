@@ -1009,7 +1009,8 @@ static int ep_compute_params(pgp_ctx* c, EpWork& w, const std::vector<double>& y
     //  exact fit's rhs rows: they are zeroed and ride along)
     if (fusedp) {
         CHK(zero_strip_launch(w.F, w.ldf, np, np, 128, st));
-        CHK(potrf_blocked(c, w.F, w.ldf, np, np + 128, true, w.Ed, np));
+        SweepJob job{w.F, w.ldf, np, np + 128, true, w.Ed, np};
+        CHK(potrf_blocked(c, job));
     } else if (rhsp) {
         // the np rows of K diag(sW) ride along in the panel solves and trailing updates (np^3 flops inside the bulk MFMA
         // launches, which at N = 4096 also gives the chain of diagonal blocks enough work to hide behind): no inverse
@@ -1017,16 +1018,16 @@ static int ep_compute_params(pgp_ctx* c, EpWork& w, const std::vector<double>& y
         CHK(zero_strip_launch(w.F, w.ldf, np, np, 128, st));
         // Sigma = K - V'V'^T accumulated under the sweep, panel by panel (lower tiles; mirrored below)
         const bool under = c->ep_sym && c->ep_sigma_under;
+        SweepJob job{w.F, w.ldf, np, np + 128};
+        job.R = w.Vd; job.ldr = np; job.nrhs2 = np;
         if (under) {
             HIP_TRY(hipMemcpyAsync(w.Sig, w.Kd, (size_t)np * np * sizeof(double), hipMemcpyDeviceToDevice, st));
-            c->fill2_C = w.Sig; c->fill2_ld = np;
+            job.rhs_C = w.Sig; job.rhs_ld = np;
         }
-        const int prc = potrf_blocked_rhs(c, w.F, w.ldf, np, np + 128, w.Vd, np, np);
-        c->fill2_C = nullptr;
-        CHK(prc);
+        CHK(potrf_blocked(c, job));
         sigma_done = under;
     }
-    else CHK(potrf_blocked(c, w.F, w.ldf, np, np));
+    else { SweepJob job{w.F, w.ldf, np, np}; CHK(potrf_blocked(c, job)); }
     int info = 0;
     HIP_TRY(hipMemcpyAsync(&info, c->info_dev, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -1101,7 +1102,8 @@ static int ep_factor_only(pgp_ctx* c, EpWork& w, const std::vector<double>& ttau
         // panels halve the number of panel steps (cfg 5, N = 4096: 17.8 -> 17.4 ms per fit); an explicit nb_outer option wins
         const int keep = c->nb_outer;
         if (keep == 0 && np >= 2048) c->nb_outer = 8;
-        const int prc = potrf_blocked(c, w.F, w.ldf, np, np);
+        SweepJob job{w.F, w.ldf, np, np};
+        const int prc = potrf_blocked(c, job);
         c->nb_outer = keep;
         CHK(prc);
     }
@@ -1320,11 +1322,7 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
             // the bulk stream (main) strip(b), U(b), fold(b), mu(b) per block.  The two meet through device counters (ep_chain_kernel).
             const long nbl = (n + EPB - 1) / EPB;
             hipStream_t sa = c->st2 ? c->st2 : st, sb = st;
-            while ((long)c->ep_ev.size() < 2) {
-                hipEvent_t e;
-                HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                c->ep_ev.push_back(e);
-            }
+            CHK(ensure_events(c->ep_ev, 2));
             unsigned* yfl = (c->yield && c->yield_flags) ? c->yield_flags : nullptr;
             const unsigned swg = (unsigned)((np + 255) / 256) * 8u;       // workgroups of one strip launch
             HIP_TRY(hipEventRecord(c->ep_ev[0], st));

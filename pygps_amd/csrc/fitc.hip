@@ -199,7 +199,8 @@ int factor_with_inverse(pgp_ctx* c, double* F, long ld, long nup, double* pack) 
     CHK(identity_upper_launch(E, ld, nup, c->st));
     double* save = c->inv16;
     c->inv16 = pack;
-    const int rc = potrf_blocked(c, F, ld, nup, nup + 128, true);
+    SweepJob job{F, ld, nup, nup + 128, true};
+    const int rc = potrf_blocked(c, job);
     c->inv16 = save;
     return rc;
 }

@@ -226,7 +226,8 @@ int pgp_node_kernel(pgp_ctx* c, int kind, const double* A, int64_t n, double p0,
         HIP_TRY(hipMemsetAsync(c->info_dev, 0, sizeof(int), st));
         double* pack_save = c->inv16;                  // the blocked driver takes the per-leaf operand images from the ctx
         c->inv16 = pack;
-        const int rc = potrf_blocked(c, M, np, np, np);
+        SweepJob job{M, np, np, np};
+        const int rc = potrf_blocked(c, job);
         c->inv16 = pack_save;
         CHK(rc);
         int info = 0;

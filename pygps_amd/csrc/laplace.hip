@@ -10,7 +10,7 @@
 // The posterior (alpha, sW, L) has EP's form, so the factor handle is built exactly like EP's and predict serves it unchanged.
 // Gradients (inf.py:530-562), with Z = sW sW' o B^-1 and S = diag(sW):
 //   g = diag(K - K Z K) / 2 = (K_ii - colsum((L^-1 S K)^2)) / 2: K diag(sW) rides as right-hand-side rows of the final
-//   factorisation (potrf_blocked_rhs, EP's rhsp form), row i of it then holds column i of L^-1 S K;
+//   factorisation (SweepJob::R, EP's rhsp form), row i of it then holds column i of L^-1 S K;
 //   u = dfhat - sW o B^-1 (sW o K dfhat), dfhat = g o d3lp;
 //   dnlZ.cov[h] = 1/2 sum((R - alpha alpha') o dK_h), R = Z - u dlp' - dlp u' (the rank-2 term is the implicit part
 //   u' dK_h dlp), written into c->Binv and summed by the exact fit's Hadamard reduce in one pass over every hyper-parameter.
@@ -242,13 +242,15 @@ int lap_factor(pgp_ctx* c, LapWork& w, double* Y) {
     CHK(ep_build_launch(w.Kd, np, w.sW, w.F, w.ldf, Y, Y ? 1 : 0, st));
     if (Y) {
         CHK(zero_strip_launch(w.F, w.ldf, np, np, 128, st));
-        const int prc = potrf_blocked_rhs(c, w.F, w.ldf, np, np + 128, Y, np, np);
-        CHK(prc);
+        SweepJob job{w.F, w.ldf, np, np + 128};
+        job.R = Y; job.ldr = np; job.nrhs2 = np;
+        CHK(potrf_blocked(c, job));
         CHK(zero_strip_launch(w.F, w.ldf, np, np, 128, st));         // the spare rows go back to the pool's contract
     } else {
         const int keep = c->nb_outer;
         if (keep == 0 && np >= 2048) c->nb_outer = 8;
-        const int prc = potrf_blocked(c, w.F, w.ldf, np, np);
+        SweepJob job{w.F, w.ldf, np, np};
+        const int prc = potrf_blocked(c, job);
         c->nb_outer = keep;
         CHK(prc);
     }

@@ -813,7 +813,7 @@ int leaf_inv_launch(const double* L, long ldl, double* W, long ldw, long wstride
 }
 
 namespace {
-// Diagonal-panel staging (see potrf_blocked in capi.hip).  The w x w diagonal block of an outer panel is factored on
+// Diagonal-panel staging (see sweep.hip).  The w x w diagonal block of an outer panel is factored on
 // its own in a small (2w x w) scratch D: top half = the block (lower part; strict upper zeroed), bottom half = identity,
 // so the leaf-level sweep over D leaves  L_D on top and  E_D = L_D^-T (upper triangular) below -- the operand that turns
 // the solve of ALL rows below the block into one MFMA GEMM  X <- X E_D.

@@ -4,7 +4,7 @@
 //
 // Layout: 1-D block-cyclic over column panels of w columns (w = 512, 1024 from N = 12288: the single-GPU sweep's panel),
 // panel p on rank p % world, one process per GPU.  A panel is stored in the LOGICAL row space of the single-GPU sweep
-// (capi.hip: potrf_blocked_v2) -- factor rows | 128 right-hand-side rows | fused-inverse rows E = L^-T -- compacted:
+// (sweep.hip) -- factor rows | 128 right-hand-side rows | fused-inverse rows E = L^-T -- compacted:
 //
 //     unfactored panel j  P_j : (np + 128) x w,  row r = logical row - j w :  [ diagonal block w | rows below | rhs 128 | E rows < j w ]
 //     solved panel p      Y_p : (np + 128) x w,  row r = logical row - (p+1) w : [ rows below | rhs 128 | E rows < (p+1) w ]
@@ -555,16 +555,12 @@ int pgp_sharded_exact_fit(pgp_ctx* c, pgp_comm* m, int kind, const double* covhy
     hipStream_t main = c->st, pan = c->st2;
     const bool pan_solve = world > 1;                // the owner's S(p+1) right behind D(p+1): its broadcast is on the critical path
     const int nev = 3 * npanel + 8;
-    while ((int)c->la_ev.size() < nev) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        c->la_ev.push_back(e);
-    }
+    CHK(ensure_events(c->la_ev, (size_t)nev));
     auto EV_S = [&](int p) { return c->la_ev[p]; };                    // Y_p produced (owner)
     auto EV_Y = [&](int p) { return c->la_ev[npanel + p]; };           // Y_p present on this rank
     auto EV_F = [&](int p) { return c->la_ev[2 * npanel + p]; };       // TU(p) has left the stream (its receive buffer is free)
-    hipEvent_t ev_stage[2] = {c->la_ev[3 * npanel], c->la_ev[3 * npanel + 1]};
-    hipEvent_t ev_a = c->la_ev[3 * npanel + 2], ev_d = c->la_ev[3 * npanel + 3];
+    hipEvent_t ev_stage[2] = {EV_F(npanel), EV_F(npanel + 1)};         // the singletons sit right behind EV_F's range
+    hipEvent_t ev_a = EV_F(npanel + 2), ev_d = EV_F(npanel + 3);
 
     // ---- inputs ----------------------------------------------------------------------------------------------------
     HIP_TRY(hipEventRecord(c->ev[0], main));

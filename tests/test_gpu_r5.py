@@ -294,7 +294,7 @@ def test_getCovMatrix_train_at_cfg3_size_in_the_gram_form(lib):
 @pytest.mark.parametrize("N", [4096, 4608, 5120, 8064, 9088])
 def test_s_pan_schedule_is_bit_identical_to_the_main_stream_solve(lib, N):
     """End of round 5: under sched=2 the panel solve S(p) runs on the panel stream behind D(p)'s leaf chain, TU_d waits for the paired
-    launch by its own event and D's stage-out runs on the main stream from a double-buffered scratch (csrc/capi.hip potrf_blocked_v2,
+    launch by its own event and D's stage-out runs on the main stream from a double-buffered scratch (csrc/sweep.hip run_sched02,
     options s_pan / s_pan_direct / s_pan_out).  Same kernels, same per-tile order: every output of Exact.evaluate
     (Core/inf.py:353-384) -- nlZ, alpha, dnlZ, the factor -- must equal the s_pan=0 schedule's BIT FOR BIT, at even and odd panel
     counts (N = 4608: 9 panels, 5120: 10) and with a partial last panel (N = 8064 = 15.75 panels, 9088 = 17.75)."""

@@ -1,4 +1,4 @@
-"""GPU: the structural zeros the exact fit's bulk trailing updates no longer multiply (csrc/gemm_tile.h, csrc/capi.hip
+"""GPU: the structural zeros the exact fit's bulk trailing updates no longer multiply (csrc/gemm_tile.h, csrc/sweep.hip
 trailing_skip; option skip_zeros).
 
 * tile level, through pgp_test_gemm_zskip: the k-clip of first-touch rows that are upper-trapezoidal in A (GemmArgs::zf_upper)
