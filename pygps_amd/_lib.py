@@ -133,6 +133,7 @@ TEST_SIGNATURES = {
     "pgp_test_hadamard": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, _dp]),
     "pgp_test_gather_sym": (C.c_int, [_vp, _dp, _i64, C.POINTER(C.c_int32), _i64, _i64, _dp, _dp, _dp, _dp]),
     "pgp_test_vote": (C.c_int, [_vp, _dp, _dp, _i64, C.c_int, C.c_int, C.c_int, _dp, _dp]),
+    "pgp_test_yield_table": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
 }
 
 _lock = threading.RLock()
@@ -267,7 +268,10 @@ class concurrent_fit_streams(object):
     """`with concurrent_fit_streams(): ...` inside `fit_stream(k)` when SEVERAL fit streams of one GPU run at the same time: the
     context's Cholesky sweep then keeps its critical path (D -> S -> TU_a) on the panel stream beside the bulk updates (the hint
     `concurrent_streams`: the sweep then runs as under `sched` = 1 UNLESS the caller has set `sched` explicitly -- an explicit
-    setting is neither overridden nor lost on exit; bit-identical results).  Measured, alternated in one process (profiles/r05_sched_ab_and_leaf_ticks.txt and three
+    setting is neither overridden nor lost on exit).  A fit beside a neighbour gives the bits of the same fit alone under the same
+    schedule; `sched` 1 gives the bits of `sched` 0, while the default schedule of a lone chain (`sched` 2) differs from both in rounding
+    -- its diagonal-block update adds the same terms in another order: <= 4e-13 relative in alpha, 2e-14 in L, 2e-15 in nlZ at
+    N = 7168 / 8192 (tests/test_gpu_side_by_side.py).  Measured, alternated in one process (profiles/r05_sched_ab_and_leaf_ticks.txt and three
     more boxes): two fit streams +0.6 ... +2 % fits/s, a lone chain -3 % -- hence only while streams run side by side."""
 
     def __enter__(self):

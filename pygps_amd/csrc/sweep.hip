@@ -236,7 +236,10 @@ static SweepPlan sweep_plan(pgp_ctx* c, const SweepMat& m, const SweepJob& job) 
     // TU_b(p) + E E'(p) -- on the main stream.  The two under-filled launches of a panel (S: ~250 tile units, TU_a: ~230) then run
     // BESIDE the previous panel's bulk launch and its tail instead of alone on the chip between two bulk launches, and D(p+1) starts
     // without waiting for them to drain a full chip.  Events: main waits for S(p) before TU_b(p); the panel stream waits for
-    // TU_b(p-1) (which brought panel p+1's columns up to date) before TU_a(p).  Same kernels, same per-tile order: bit-identical.
+    // TU_b(p-1) (which brought panel p+1's columns up to date) before TU_a(p).  Same launches with the same arguments as sched 0, on other
+    // streams: bit-identical to sched 0.  NOT to sched 2, whose TU_d runs the next panel's diagonal block as 64-tiles: those start their
+    // accumulators from C, the 128 x 128 LDS-DMA tiles of TU_a fold C in during the k-loop (gemm_tile.h, "lazy C") -- the same sum in
+    // another order, a few 1e-13 relative in alpha (tests/test_gpu_side_by_side.py pins both statements).
     // sched 1 is what fit streams that run side by side ask for (_lib.concurrent_fit_streams); it pays from N ~ 7000 on (two streams,
     // N = 8192: 109.5 vs 107.7 fits/s with sched 2) and costs below (N = 6144: 218.5 vs 225.3; N = 4096: 467 vs 513 / 521 with
     // sched 2 / 0): smaller sweeps take the default schedule instead

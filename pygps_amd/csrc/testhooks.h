@@ -56,6 +56,9 @@ int pgp_test_gather_sym(pgp_ctx* ctx, const double* K, int64_t n, const int32_t*
    (ns x n_class) before the normalisation, norm_out (optional) after it */
 int pgp_test_vote(pgp_ctx* ctx, const double* fmu, const double* fs2, int64_t ns, int n_class, int ci, int cj, double* votes_out,
                   double* norm_out);
+/* the device's yield table (capi.hip: one per device, shared by every context on it; 4096 words, one per CU key) read back to
+   out4096 once the context's own streams are idle.  Reads only, launches nothing.  -2: the context has no table */
+int pgp_test_yield_table(pgp_ctx* ctx, uint32_t* out4096);
 #ifdef __cplusplus
 }
 #endif

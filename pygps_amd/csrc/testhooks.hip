@@ -844,3 +844,17 @@ extern "C" int pgp_test_hadamard(pgp_ctx* c, int kind, const double* hyp, int nc
     HIP_TRY(hipStreamSynchronize(st));
     return PGP_OK;
 }
+
+// self-test hook: the device's yield table as the host sees it once this context's streams have drained.  A chain kernel adds 1 to
+// its CU's word on entry and takes it off on exit (common.h pgp_yield_mark), so a quiescent device reads all zeros; a word left
+// non-zero makes every bulk workgroup that lands on that CU sleep through gemm_yield_wait from then on, with correct results.
+extern "C" int pgp_test_yield_table(pgp_ctx* c, uint32_t* out4096) {
+    if (!c || !out4096) return -1;
+    if (!c->yield_flags) return -2;
+    GateShared device_gate_hold(c);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    if (c->st2) HIP_TRY(hipStreamSynchronize(c->st2));
+    HIP_TRY(hipMemcpy(out4096, c->yield_flags, 4096 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return PGP_OK;
+}
