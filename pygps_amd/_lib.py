@@ -113,6 +113,8 @@ TEST_SIGNATURES = {
                                        _i64]),
     "pgp_test_gemm_zskip": (C.c_int, [_vp] + [C.c_int] * 5 + [C.c_double, C.c_double, _dp, _i64, _dp, _i64, _dp, _dp, _i64,
                                       C.c_int, C.c_int, C.c_int]),
+    "pgp_test_gemm_pair": (C.c_int, [_vp, C.c_double, C.c_double, _dp, _i64, _dp, _i64, _dp, _dp, _i64, C.c_int, C.c_int, C.c_int,
+                                     C.c_int]),
     "pgp_test_gemm_skip_wait": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.POINTER(C.c_int)]),
     "pgp_test_probit_hazard": (C.c_int, [_vp, _dp, _dp, C.c_int]),

@@ -192,6 +192,7 @@ int pgp_set_option(pgp_ctx* c, const char* name, int value) {
     if (!strcmp(name, "trtri_small_tile_below")) { c->trtri_small_tile_below = value; return PGP_OK; }
     if (!strcmp(name, "xcd_order")) { c->xcd_order = value; return PGP_OK; }
     if (!strcmp(name, "gemm_dbg")) { if (value & ~(64 | 256 | 512)) return -2; c->gemm_dbg = value; return PGP_OK; }
+    if (!strcmp(name, "tile_ring")) { if (value < 0 || value > 1) return -2; c->tile_ring = value; return PGP_OK; }
     if (!strcmp(name, "lookahead")) { c->lookahead = value; return PGP_OK; }
     if (!strcmp(name, "leaf_first")) { c->leaf_first = value; return PGP_OK; }
     if (!strcmp(name, "leaf_pivot")) { if (value < 0 || value > 2) return -2; c->leaf_pivot = value; return PGP_OK; }
@@ -658,6 +659,7 @@ static int gemm_prepare(pgp_ctx* c, GemmArgs& g) {
         // the chain's own small products mark their CUs (the caller presets role 2); every bulk (128-tile, LDS-DMA) launch polls
         if (g.yield_role != 2) g.yield_role = gemm_f64_uses_dma(g) ? 1 : 0;
     } else g.yield_role = 0;
+    g.ring = c->tile_ring && gemm_f64_uses_dma(g) ? 1 : 0;      // the context's option decides, for every launch that goes through here
     if (c->gemm_trace && gemm_f64_uses_dma128(g) && g.batch == 1) {
         const long mt = g.M / 128, nt = g.N / 128;
         const long nb = g.order ? g.norder : (g.tri == 2 ? mt * (mt + 1) / 2 : mt * nt);

@@ -54,6 +54,7 @@ struct GemmArgs {
     int order_z;            // 1: the list spans a whole batch -- ti carries the batch index in its bits 16.. (grid.z = 1): a shrinking
                             // batch dispatches exactly its tiles instead of batch x (tiles of the largest product)
     int dbg;                // variant bits (pgp_ctx::gemm_dbg): 64 LDS-DMA staging, 256 lazy C, 512 16-byte epilogue stores
+    int ring;               // LDS-DMA tiles: stage through the four-slot ring (gemm_tile.h, RING; pgp_ctx::tile_ring).  Same results bit for bit
     double flops;           // algorithmic flops of this launch (for profiling; filled by caller)
     // Two-piece row spaces (the factor rows and the fused-inverse rows of a Cholesky sweep live in separate buffers so
     // that a posterior handle only keeps the factor).  Tile rows i0 >= *_split (relative to the operand's row 0, a
@@ -89,7 +90,7 @@ struct GemmArgs {
     // anything -- an operand another RESIDENT kernel publishes (EP's sweep kernel: W of the block).  Bounded; a timeout sets *wait_err.
     unsigned* wait_flag; unsigned wait_target; unsigned* wait_err;
     // phase stamps of every workgroup (pgp_test_gemm_trace; nullptr otherwise): 8 words per block -- 100 MHz wall clock at kernel
-    // entry, (unused), behind the k-loop, with the epilogue's stores issued, with them acknowledged; the CU key; the shader-clock
+    // entry, behind the lazy-C prologue (k-step 16; 0 if the tile has none), behind the k-loop, with the epilogue's stores issued, with them acknowledged; the CU key; the shader-clock
     // counter at entry and at the end
     long long* trace;
 };

@@ -184,6 +184,10 @@ struct pgp_ctx {
     // GEMM variant bits: 64 LDS-DMA operand staging, 256 lazy C (fetched during the k-loop into the registers the DMA
     // frees), 512 16-byte epilogue stores -- the measured-best set; clearing a bit selects the plain form (tests)
     int gemm_dbg = 64 | 256 | 512;
+    // option "tile_ring": 1 = every LDS-DMA launch stages through the four-slot ring (GemmArgs::ring; gemm_tile.h), 0 = the plain
+    // two-buffer loop.  Same bits either way.  On by measurement (EXPERIMENTS.md): a workgroup alone on its CU 1.31 -> 1.19 x its MFMA
+    // cycles, the stand-alone K = 512 product +2.7 %; ring only for launches under two workgroups per CU was built and measured no better
+    int tile_ring = 1;
     int xcd_order = 0;    // 1: XCD-aware super-tile order for bulk launches (see gemm_prof): -40 % FETCH per launch, 1-3 % slower
     // options
     int nb_outer = 0;     // leaves (128 columns each) per outer panel -> trailing update K = 128 nb_outer; 0 = automatic (4, or 8 from N = 12288)

@@ -72,7 +72,7 @@ __device__ __forceinline__ bool decode_tile(const GemmArgs& g, int b, int T, int
     return true;
 }
 
-template <int TM, int TN, bool AKC, bool BKC, bool DMA = false, bool YIELD = false>
+template <int TM, int TN, bool AKC, bool BKC, bool DMA = false, bool YIELD = false, bool RING = false>
 __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     if (g.trace) {                                   // every lane the same words: no divergent branch in here
@@ -98,19 +98,19 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs g) {
     }
     if (!YIELD && g.yield_role == 2) {               // one of the chain's own small products: its CU's bulk workgroups give way
         pgp_yield_mark(g.yield_flags, +1);
-        gemm_tile_ns::gemm_tile<TM, TN, AKC, BKC, DMA, false>(g, ti, tj, bz, smem, (int)(blockIdx.x + gridDim.x * blockIdx.z));
+        gemm_tile_ns::gemm_tile<TM, TN, AKC, BKC, DMA, false, RING>(g, ti, tj, bz, smem, (int)(blockIdx.x + gridDim.x * blockIdx.z));
         __syncthreads();
         pgp_yield_mark(g.yield_flags, -1);
         return;
     }
-    gemm_tile_ns::gemm_tile<TM, TN, AKC, BKC, DMA, YIELD>(g, ti, tj, bz, smem, (int)(blockIdx.x + gridDim.x * blockIdx.z));
+    gemm_tile_ns::gemm_tile<TM, TN, AKC, BKC, DMA, YIELD, RING>(g, ti, tj, bz, smem, (int)(blockIdx.x + gridDim.x * blockIdx.z));
 }
 
 // TWO independent bulk products in ONE launch (round 4: the trailing update TU_b(p) and panel p's share of E E'): workgroups
 // [0, na) run a's tiles, the rest b's.  Each launch of a few hundred tiles ends in a tail during which the chip drains (the next
 // launch of an in-order stream starts when the last workgroup has gone); merging the pair halves the number of tails per panel.
 // Both argument sets live in the kernel-argument segment; the workgroup picks one by a uniform pointer select.
-template <bool YIELD>
+template <bool YIELD, bool RING = false>
 __global__ __launch_bounds__(256, 2) void gemm_f64_pair_kernel(GemmArgs a, GemmArgs b, int na) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     // two copies of the tile code, each reading ITS argument set straight from the kernel-argument segment: a pointer select
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_pair_kernel(GemmArgs a, GemmA
         }
         int ti, tj;
         if (!decode_tile(g, bid, 128, 128, ti, tj)) return;
-        gemm_tile_ns::gemm_tile<128, 128, false, false, true, YIELD>(g, ti, tj, 0, smem, bid);
+        gemm_tile_ns::gemm_tile<128, 128, false, false, true, YIELD, RING>(g, ti, tj, 0, smem, bid);
     };
     if ((int)blockIdx.x < na) run(a, (int)blockIdx.x);
     else run(b, (int)blockIdx.x - na);
@@ -135,32 +135,35 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_pair_kernel(GemmArgs a, GemmA
 // BLOCKS on the engine whose turn it is (EXPERIMENTS.md, round 3): a grid of tiles that last 1x .. 64x leaves the slots of the
 // short ones idle until the rotation comes round -- M = N = K = 8192 clipped to the triangle ran at 47 TF of algorithmic flops
 // against 75 TF unclipped (tools/_gemm_clip.py).
-template <bool YIELD>
+template <bool YIELD, bool RING = false>
 __global__ __launch_bounds__(256, 2) void gemm_f64_fold_kernel(GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int mt = g.M / 128, half = (mt + 1) / 2;
     const int r = (int)blockIdx.x % half, tj = (int)blockIdx.x / half;
     const int hi = mt - 1 - r;
     const long bz = blockIdx.z;
-    gemm_tile_ns::gemm_tile<128, 128, false, false, true, YIELD>(g, hi, tj, bz, smem, 0);
+    gemm_tile_ns::gemm_tile<128, 128, false, false, true, YIELD, RING>(g, hi, tj, bz, smem, 0);
     if (hi != r) {
         __syncthreads();                             // (the first tile's last LDS reads are over before the second tile stages)
-        gemm_tile_ns::gemm_tile<128, 128, false, false, true, YIELD>(g, r, tj, bz, smem, 0);
+        gemm_tile_ns::gemm_tile<128, 128, false, false, true, YIELD, RING>(g, r, tj, bz, smem, 0);
     }
 }
 
-template <int T, bool AKC, bool BKC, bool DMA = false, bool YIELD = false>
+// the LDS-DMA tiles keep one spare 16-byte word behind their stage buffers (the trace stamp taken inside the k-loop)
+constexpr size_t DMA_SPARE = 16;
+
+template <int T, bool AKC, bool BKC, bool DMA = false, bool YIELD = false, bool RING = false>
 int launch_t(const GemmArgs& g, hipStream_t st) {
     constexpr int SK = BK + 2;
     constexpr int ASZ = AKC ? T * SK : BK * (T + 16);
     constexpr int BSZ = BKC ? T * SK : BK * (T + 16);
-    const size_t shm = 2 * (ASZ + BSZ) * sizeof(double);
+    const size_t shm = 2 * (ASZ + BSZ) * sizeof(double) + (DMA ? DMA_SPARE : 0);
     const int mt = g.M / T, nt = g.N / T;
     unsigned nblk = (g.tri == 2) ? (unsigned)((long)mt * (mt + 1) / 2) : (unsigned)(mt * nt);
     if (g.order) nblk = (unsigned)g.norder;
     dim3 grid(nblk, 1, (g.batch > 0 && !g.order_z) ? g.batch : 1);
-    func_max_dynamic_lds((const void*)gemm_f64_kernel<T, T, AKC, BKC, DMA, YIELD>, shm);
-    hipLaunchKernelGGL((gemm_f64_kernel<T, T, AKC, BKC, DMA, YIELD>), grid, dim3(256), shm, st, g);
+    func_max_dynamic_lds((const void*)gemm_f64_kernel<T, T, AKC, BKC, DMA, YIELD, RING>, shm);
+    hipLaunchKernelGGL((gemm_f64_kernel<T, T, AKC, BKC, DMA, YIELD, RING>), grid, dim3(256), shm, st, g);
     return hipGetLastError() == hipSuccess ? PGP_OK : PGP_ERR_HIP;
 }
 
@@ -169,13 +172,13 @@ static bool dma_ok(const GemmArgs& g);
 static bool dma1264_ok(const GemmArgs& g) {
     return g.tile == 1264 && dma_ok(g) && !g.tri && !g.order && g.batch <= 1 && !g.order_z && (g.N % 64) == 0 && (g.M % 128) == 0 && g.kmode == KM_FULL;
 }
-template <bool YIELD>
+template <bool YIELD, bool RING>
 int launch_1264(const GemmArgs& g, hipStream_t st) {
     constexpr int SA_ = 128 + 16;
-    const size_t shm = 2 * (BK * SA_ + (BK / 2) * SA_) * sizeof(double);
+    const size_t shm = 2 * (BK * SA_ + (BK / 2) * SA_) * sizeof(double) + DMA_SPARE;
     dim3 grid((unsigned)((g.M / 128) * (g.N / 64)), 1, 1);
-    func_max_dynamic_lds((const void*)gemm_f64_kernel<128, 64, false, false, true, YIELD>, shm);
-    hipLaunchKernelGGL((gemm_f64_kernel<128, 64, false, false, true, YIELD>), grid, dim3(256), shm, st, g);
+    func_max_dynamic_lds((const void*)gemm_f64_kernel<128, 64, false, false, true, YIELD, RING>, shm);
+    hipLaunchKernelGGL((gemm_f64_kernel<128, 64, false, false, true, YIELD, RING>), grid, dim3(256), shm, st, g);
     return hipGetLastError() == hipSuccess ? PGP_OK : PGP_ERR_HIP;
 }
 
@@ -206,29 +209,35 @@ bool gemm_f64_pair_ok(const GemmArgs& a, const GemmArgs& b) {
     auto plain = [](const GemmArgs& g) {
         return g.M > 0 && g.N > 0 && g.tile != 64 && dma_ok(g) && g.batch <= 1 && !g.order_z && !g.wait_flag && g.yield_role != 2;
     };
-    return plain(a) && plain(b) && (a.yield_role == 1 && a.yield_flags) == (b.yield_role == 1 && b.yield_flags);
+    return plain(a) && plain(b) && (a.yield_role == 1 && a.yield_flags) == (b.yield_role == 1 && b.yield_flags) && !a.ring == !b.ring;
 }
 int gemm_f64_launch_pair(const GemmArgs& a, const GemmArgs& b, hipStream_t st) {
     if (!gemm_f64_pair_ok(a, b)) return -2;
     constexpr int SA_ = 128 + 16;
-    const size_t shm = 2 * (2 * BK * SA_) * sizeof(double);
+    const size_t shm = 2 * (2 * BK * SA_) * sizeof(double) + DMA_SPARE;
     const unsigned na = launch_blocks(a), nb = launch_blocks(b);
     const bool yield = a.yield_role == 1 && a.yield_flags;
-    func_max_dynamic_lds((const void*)(yield ? gemm_f64_pair_kernel<true> : gemm_f64_pair_kernel<false>), shm);
-    if (yield) hipLaunchKernelGGL(gemm_f64_pair_kernel<true>, dim3(na + nb), dim3(256), shm, st, a, b, (int)na);
-    else hipLaunchKernelGGL(gemm_f64_pair_kernel<false>, dim3(na + nb), dim3(256), shm, st, a, b, (int)na);
+    auto go = [&](auto kern) {
+        func_max_dynamic_lds((const void*)kern, shm);
+        hipLaunchKernelGGL(kern, dim3(na + nb), dim3(256), shm, st, a, b, (int)na);
+    };
+    if (a.ring) { if (yield) go(gemm_f64_pair_kernel<true, true>); else go(gemm_f64_pair_kernel<false, true>); }
+    else { if (yield) go(gemm_f64_pair_kernel<true, false>); else go(gemm_f64_pair_kernel<false, false>); }
     return hipGetLastError() == hipSuccess ? PGP_OK : PGP_ERR_HIP;
 }
 
 static int launch_fold(const GemmArgs& g, hipStream_t st) {
     constexpr int SA_ = 128 + 16;
-    const size_t shm = 2 * (2 * BK * SA_) * sizeof(double);
+    const size_t shm = 2 * (2 * BK * SA_) * sizeof(double) + DMA_SPARE;
     const int mt = g.M / 128, nt = g.N / 128;
     dim3 grid((unsigned)(((mt + 1) / 2) * nt), 1, g.batch > 0 ? g.batch : 1);
     const bool yield = g.yield_role == 1 && g.yield_flags;
-    func_max_dynamic_lds((const void*)(yield ? gemm_f64_fold_kernel<true> : gemm_f64_fold_kernel<false>), shm);
-    if (yield) hipLaunchKernelGGL(gemm_f64_fold_kernel<true>, grid, dim3(256), shm, st, g);
-    else hipLaunchKernelGGL(gemm_f64_fold_kernel<false>, grid, dim3(256), shm, st, g);
+    auto go = [&](auto kern) {
+        func_max_dynamic_lds((const void*)kern, shm);
+        hipLaunchKernelGGL(kern, grid, dim3(256), shm, st, g);
+    };
+    if (g.ring) { if (yield) go(gemm_f64_fold_kernel<true, true>); else go(gemm_f64_fold_kernel<false, true>); }
+    else { if (yield) go(gemm_f64_fold_kernel<true, false>); else go(gemm_f64_fold_kernel<false, false>); }
     return hipGetLastError() == hipSuccess ? PGP_OK : PGP_ERR_HIP;
 }
 
@@ -237,9 +246,15 @@ int gemm_f64_launch(const GemmArgs& g, hipStream_t st) {
     if (g.tile == 64) return launch_l<64>(g, st);
     if (g.fold_rows && g.tile == 128 && dma_ok(g) && !g.tri && !g.order && !g.order_z && !g.wait_flag && g.yield_role != 2 && !g.trace)
         return launch_fold(g, st);
-    if (dma1264_ok(g)) return (g.yield_role == 1 && g.yield_flags) ? launch_1264<true>(g, st) : launch_1264<false>(g, st);
+    const bool yield = g.yield_role == 1 && g.yield_flags;
+    if (dma1264_ok(g)) {
+        if (g.ring) return yield ? launch_1264<true, true>(g, st) : launch_1264<false, true>(g, st);
+        return yield ? launch_1264<true, false>(g, st) : launch_1264<false, false>(g, st);
+    }
     // LDS-DMA staging (dbg bit 64): 128 x 128 tiles of M-contiguous operands, whole 16-deep k-tiles
-    if (dma_ok(g)) return (g.yield_role == 1 && g.yield_flags) ? launch_t<128, false, false, true, true>(g, st)
-                                                               : launch_t<128, false, false, true>(g, st);
+    if (dma_ok(g)) {
+        if (g.ring) return yield ? launch_t<128, false, false, true, true, true>(g, st) : launch_t<128, false, false, true, false, true>(g, st);
+        return yield ? launch_t<128, false, false, true, true>(g, st) : launch_t<128, false, false, true>(g, st);
+    }
     return launch_l<128>(g, st);
 }

@@ -30,6 +30,30 @@ __device__ __forceinline__ const double* uniform_ptr(const double* p) {
 }
 template <int V> struct IC { static constexpr int value = V; };
 
+// The staging ring's waits (gemm_tile<..., RING>): its LDS-DMA pieces stay in flight ACROSS the workgroup barrier, so the wait is a
+// counted one -- at most N of this wave's vector-memory operations may still be outstanding, the oldest ones have landed -- and the
+// barrier a raw s_barrier (a __syncthreads() fence would drain the counter).  lgkmcnt(0): this wave's fragment reads of the slot
+// that is refilled right behind the barrier have returned.  hipcc does not count loads issued from asm, so every vector-memory
+// load of the ring's k-loop (pieces, the lazy C chunk, the yield word) is issued from asm and waited for here, by count.
+template <int N>
+__device__ __forceinline__ void ring_wait() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
+template <int N>
+__device__ __forceinline__ void ring_wait_barrier() {
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(N) : "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+__device__ __forceinline__ void ring_load_f64(double& d, const double* p) {
+    asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(d) : "v"(p) : "memory");
+}
+// (a value loaded from asm is not there yet: nothing may read it ahead of the counted wait -- the empty statement makes every later
+//  use depend on a point BEHIND the wait it follows.  Between the load and ring_landed the register is formally live and the compiler
+//  is free to copy or spill it, which would read it early; nothing in the language forbids that.  The emitted gfx950 code has been
+//  read for it -- the only vmcnt waits inside the k-loop are the counted ones -- and the bit-for-bit tests of tests/test_gpu_tile_ring.py
+//  are the standing guard: a compiler that moved such a register would fail them)
+__device__ __forceinline__ void ring_landed(double& d) { asm volatile("" : "+v"(d)); }
+__device__ __forceinline__ void ring_landed(unsigned& d) { asm volatile("" : "+v"(d)); }
+
 // value of the neighbouring lane (l ^ 1): DPP quad_perm [1,0,3,2] on both halves
 __device__ __forceinline__ double swap_adjacent(double v) {
     const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0xB1, 0xF, 0xF, false);
@@ -49,8 +73,15 @@ __device__ __noinline__ void gemm_yield_wait(const unsigned* yf) {
 
 // A stage of the k-loop is one basic block: nothing run-time selectable is tested inside it (YIELD adds one load per stage,
 // issued beside the LDS-DMA pieces and consumed after the stage's barrier, and a never-taken branch).
-template <int TM, int TN, bool AKC, bool BKC, bool DMA = false, bool YIELD = false>
+// RING (LDS-DMA tiles only; GemmArgs::ring): the same two stage buffers run as a ring of FOUR slots of 8 k-rows.  A slot is refilled
+// as soon as its last reader has passed the slot's barrier, the pieces of slot h + 3 are in flight while slot h is multiplied: a
+// piece has six k-substeps (1.5 stages) to land instead of four, and the lazy C chunk of a stage is waited for behind the NEXT
+// stage's barrier instead of this one's.  What is multiplied, in which order, and the k-step at which C is folded in do not change:
+// the results are the plain loop's bit for bit.  It pays where a workgroup has its CU to itself (four waves cannot cover an HBM
+// round trip of one stage); see DESIGN.md section 3.
+template <int TM, int TN, bool AKC, bool BKC, bool DMA = false, bool YIELD = false, bool RING = false>
 __device__ __forceinline__ void gemm_tile(const GemmArgs& g, int ti, int tj, long bz, double* __restrict__ smem, int wg = 0) {
+    static_assert(!RING || DMA, "the staging ring is an LDS-DMA loop");
     static_assert(!DMA || (!AKC && !BKC && TM == 128 && (TN == 128 || TN == 64)), "LDS-DMA staging: M-contiguous operands, 128 x 128 or 128 x 64 tiles");
     // BH (round 6, the 128 x 64 LDS-DMA tile: TWO workgroups per CU for a launch of fewer 128 x 128 tiles than CUs): a k-row of the B
     // operand is 64 doubles = half a 1 KiB LDS-DMA piece, so one piece carries the k-rows (k, k + 4) -- lanes 0-31 fetch row k,
@@ -202,6 +233,26 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, int ti, int tj, lon
             for (int p = 0; p < 4; ++p) { da[p] += dstep_a; db[p] += dstep_b; }
         }
     };
+    // RING: the pieces of ONE ring slot = half hf (8 k-rows) of stage buffer buf: the same pieces at the same LDS addresses as
+    // dma_stage's, k-rows wave and wave + 4 of the half (BH: one B piece carries both)
+    constexpr int P = BH ? 3 : 4;                  // pieces per wave and slot
+    auto ring_piece = [&](auto bufc, auto halfc, auto jc) __attribute__((always_inline)) {        // piece j of the slot, and the bump of its row base
+        constexpr int O = decltype(bufc)::value * STAGE * 8, hf = decltype(halfc)::value, j = decltype(jc)::value;
+        if constexpr (DMA && BH) {
+            if constexpr (j == 0) { lds_dma_1k_s<O + (8 * hf) * SA * 8>(dvoff, da[2 * hf], lds_w); da[2 * hf] += dstep_a; }
+            if constexpr (j == 1) { lds_dma_1k_s<O + ASZ * 8 + (4 * hf) * SB * 8>(dvoff_b, db[hf], lds_w); db[hf] += dstep_b; }
+            if constexpr (j == 2) { lds_dma_1k_s<O + (8 * hf + 4) * SA * 8>(dvoff, da[2 * hf + 1], lds_w); da[2 * hf + 1] += dstep_a; }
+        } else if constexpr (DMA) {
+            if constexpr (j == 0) { lds_dma_1k_s<O + (8 * hf) * SA * 8>(dvoff, da[2 * hf], lds_w); da[2 * hf] += dstep_a; }
+            if constexpr (j == 1) { lds_dma_1k_s<O + ASZ * 8 + (8 * hf) * SB * 8>(dvoff, db[2 * hf], lds_w); db[2 * hf] += dstep_b; }
+            if constexpr (j == 2) { lds_dma_1k_s<O + (8 * hf + 4) * SA * 8>(dvoff, da[2 * hf + 1], lds_w); da[2 * hf + 1] += dstep_a; }
+            if constexpr (j == 3) { lds_dma_1k_s<O + ASZ * 8 + (8 * hf + 4) * SB * 8>(dvoff, db[2 * hf + 1], lds_w); db[2 * hf + 1] += dstep_b; }
+        }
+    };
+    auto ring_issue = [&](auto bufc, auto halfc) __attribute__((always_inline)) {
+        ring_piece(bufc, halfc, IC<0>{}); ring_piece(bufc, halfc, IC<1>{}); ring_piece(bufc, halfc, IC<2>{});
+        if constexpr (P == 4) ring_piece(bufc, halfc, IC<3>{});
+    };
     auto gload = [&](int) {
 #pragma unroll
         for (int p = 0; p < AV; ++p) { ra[p] = *(const double2_t*)pa[p]; pa[p] += astep; }
@@ -243,7 +294,31 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, int ti, int tj, lon
         }
     };
 
+    // RING, lazy C: chunk c (two accumulator tiles of this wave, as in the plain loop) is folded in at k-step 2c + 1 (BH: 8 h + 2c + 1 for
+    // the waves of column half h) and fetched six k-substeps ahead of that: behind barrier A of stage 2c - 1, the first one in the
+    // prologue.  The counter retires in order, so a load can be outstanding no longer than the pieces issued right behind it.
+    double cr[8];
+    const int ring_half = __builtin_amdgcn_readfirstlane(wave >> 1);
+    auto ring_cact = [&](int fold_step) __attribute__((always_inline)) { return !BH || ring_half == (fold_step >> 3); };     // does this wave fold a chunk at that k-step?
+    auto ring_cload = [&](int chunk) __attribute__((always_inline)) {
+        const int in = chunk / (FM / 2), hf = chunk % (FM / 2);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const double* cp = Cin + (long)(i0 + wm + (2 * hf + q) * 16 + l15) + (long)(j0 + wn + in * 16 + l4) * ldcin;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) ring_load_f64(cr[4 * q + r], cp + (long)(4 * r) * ldcin);
+        }
+    };
     if (k0 < k1) {
+        if constexpr (RING) {                     // slots 0, 1, 2 go out, the first lazy C chunk behind them; slot 0 has landed when at
+            ring_issue(IC<0>{}, IC<0>{});         // most those are outstanding
+            ring_issue(IC<0>{}, IC<1>{});
+            if (k0 + BK < k1) {
+                ring_issue(IC<1>{}, IC<0>{});
+                if (lazyc && ring_cact(1)) { ring_cload(0); ring_wait_barrier<2 * P + 8>(); }
+                else ring_wait_barrier<2 * P>();
+            } else ring_wait_barrier<P>();
+        } else {
         if constexpr (DMA) {
             dma_stage(IC<0>{});
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -252,6 +327,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, int ti, int tj, lon
             sstore(0);
         }
         __syncthreads();
+        }
         // fragments are double-buffered in registers: the LDS reads of k-substep ks+1 are issued BEFORE the 16 MFMAs of
         // substep ks, so their latency hides behind 1024 cycles of matrix work.  The same holds ACROSS the stage barrier:
         // the last substep's MFMAs of a stage are held back until after the barrier and issued behind the first fragment
@@ -308,7 +384,112 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, int ti, int tj, lon
             __builtin_amdgcn_sched_barrier(0);    // (keep the reads AHEAD of the MFMAs: the scheduler sinks them behind otherwise)
             mfmas((NS - 1) & 1);                  // ... the held-back last substep of this one
         };
+        // RING: a stage is two ring slots, s the stage's number, slot 2s its first half.  In program order
+        //   [yield word]  substep 0 with the pieces of slot 2s+3 | slot 2s+1 landed, barrier A | [C chunk] substep 1 with the pieces of
+        //   slot 2s+4, substep 2 | slot 2s+2 and the yield word landed, barrier B | substep 3 (held back, as in the plain loop)
+        // The pieces go out BETWEEN the MFMAs of a substep, one behind every other MFMA: a wave that has its SIMD to itself issues
+        // in order, and a block of forty scalar instructions between two substeps is forty instructions of idle matrix pipe.
+        // Every wait names what MAY still be outstanding behind the thing it waits for, oldest first; a stage near the end of the
+        // k-range issues fewer pieces and waits for more than it must (never for less).
+        auto mfma1 = [&](int slot, auto ic) __attribute__((always_inline)) {
+            constexpr int i = decltype(ic)::value, in = i / FM, im = i % FM;
+            acc[im][in] = __builtin_amdgcn_mfma_f64_16x16x4f64(fb[slot][in], fa[slot][im], acc[im][in], 0, 0, 0);
+        };
+        auto mfmas_p = [&](int slot, bool go, auto bufc, auto halfc) __attribute__((always_inline)) {   // mfmas(slot), the slot's pieces (if go) spread over it
+            auto one = [&](auto ic) __attribute__((always_inline)) {
+                constexpr int i = decltype(ic)::value;
+                mfma1(slot, ic);
+                if constexpr (i % 2 == 1 && i / 2 < P) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (go) ring_piece(bufc, halfc, IC<i / 2>{});
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            };
+            one(IC<0>{}); one(IC<1>{}); one(IC<2>{}); one(IC<3>{}); one(IC<4>{}); one(IC<5>{}); one(IC<6>{}); one(IC<7>{});
+            if constexpr (FM * FN == 16) {
+                one(IC<8>{}); one(IC<9>{}); one(IC<10>{}); one(IC<11>{}); one(IC<12>{}); one(IC<13>{}); one(IC<14>{}); one(IC<15>{});
+            }
+        };
+        // cp: 8 if a C chunk this wave fetched in the stage before (or the prologue) may still be outstanding; cmchunk: the chunk to
+        // fetch behind barrier A (-1: none; a constant once the prologue is unrolled), cmact: this wave fetches it
+        auto rstep = [&](int kt, auto bufc, auto pollc, int cp, int cmchunk, bool cmact) __attribute__((always_inline)) {
+            constexpr int buf = decltype(bufc)::value;
+            constexpr bool POLL = YIELD && decltype(pollc)::value != 0;
+            constexpr int Y = POLL ? 1 : 0;
+            const bool more = kt + BK < k1, more2 = kt + 2 * BK < k1;
+            unsigned yv = 0u;
+            if constexpr (POLL) asm volatile("global_load_dword %0, %1, %2 sc1" : "=v"(yv) : "v"(0u), "s"(yf) : "memory");
+            ldfrag(buf, 1, 1);
+            mfmas_p(0, more, IC<(buf ^ 1)>{}, IC<1>{});          // slot 2s+3: its last reader passed barrier B of the stage before
+            if (more) {                                // behind slot 2s+1: slot 2s+2, the pending C chunk, the yield word, slot 2s+3
+                if (cp != 0) ring_wait_barrier<2 * P + Y + 8>();
+                else ring_wait_barrier<2 * P + Y>();
+            } else ring_wait_barrier<0>();
+            const bool cm = cmchunk >= 0 && cmact;
+            if (cm) ring_cload(cmchunk);
+            ldfrag(buf, 2, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            mfmas_p(1, more2, IC<buf>{}, IC<0>{});               // slot 2s+4: the first half of this buffer was last read ahead of barrier A
+            ldfrag(buf, 3, 1);
+            mfmas(0);
+            if (more2) {                               // behind slot 2s+2 and the yield word: slot 2s+3, the C chunk of this stage, slot 2s+4
+                if (cm) ring_wait_barrier<2 * P + 8>();          // (a chunk pending from the stage before is older than slot 2s+2: it has landed)
+                else ring_wait_barrier<2 * P>();
+            } else if (more) ring_wait_barrier<P>();
+            else ring_wait_barrier<0>();
+            if constexpr (POLL) { ring_landed(yv); if (__builtin_amdgcn_readfirstlane(yv) != 0u) gemm_yield_wait(yf); }
+            if (more) ldfrag(buf ^ 1, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            mfmas(1);
+        };
         int kt = k0;
+        if constexpr (RING) {
+            if (lazyc) {          // the plain loop's lazy-C prologue: the same chunks, folded in at the same k-steps
+                static_assert(FM == 4 && (FN == 4 || FN == 2), "lazy C: 64-row wave tiles, 64 or 32 columns");
+                auto lzstep = [&](auto stc) __attribute__((always_inline)) {           // (st a constant expression: every accumulator index is one)
+                    constexpr int st = decltype(stc)::value;
+                    constexpr int chunk = (BH ? (st & 7) : st) >> 1, in = chunk / (FM / 2), hf = chunk % (FM / 2);
+                    if constexpr ((st & 1) != 0) {
+                        if (ring_cact(st)) {          // barrier B of the stage before let only the pieces of slots 2s+1 and 2s+2 stay
+                                                      // outstanding, and the chunk is older than both: it went out two stages back, ahead
+                                                      // of slot 2s (chunk 0, st = 1: in the prologue, BEHIND slot 2 but ahead of slot 3)
+#pragma unroll
+                            for (int i = 0; i < 8; ++i) ring_landed(cr[i]);
+#pragma unroll
+                            for (int q = 0; q < 2; ++q)
+#pragma unroll
+                                for (int r = 0; r < 4; ++r) acc[2 * hf + q][in][r] = fma(ab, cr[4 * q + r], acc[2 * hf + q][in][r]);
+                        }
+                        // the chunk folded in at k-step st + 2 goes out behind this stage's barrier A
+                        rstep(kt, IC<1>{}, IC<0>{}, 0, st + 2 < LZ ? (BH ? ((st + 2) & 7) : (st + 2)) >> 1 : -1, ring_cact(st + 2));
+                    } else {
+                        const int cp = ring_cact(st + 1) ? 8 : 0;
+                        if constexpr ((st & 3) == 0) rstep(kt, IC<0>{}, IC<1>{}, cp, -1, false);
+                        else rstep(kt, IC<0>{}, IC<0>{}, cp, -1, false);
+                    }
+                    kt += BK;
+                };
+                static_assert(LZ == 16, "the prologue is written out");
+                lzstep(IC<0>{}); lzstep(IC<1>{}); lzstep(IC<2>{}); lzstep(IC<3>{}); lzstep(IC<4>{}); lzstep(IC<5>{}); lzstep(IC<6>{}); lzstep(IC<7>{});
+                lzstep(IC<8>{}); lzstep(IC<9>{}); lzstep(IC<10>{}); lzstep(IC<11>{}); lzstep(IC<12>{}); lzstep(IC<13>{}); lzstep(IC<14>{}); lzstep(IC<15>{});
+                if (g.trace) smem[2 * STAGE] = __longlong_as_double((long long)wall_clock64());   // (the spare LDS word: see below)
+            }
+            while (kt < k1) {
+                rstep(kt, IC<0>{}, IC<1>{}, 0, -1, false);
+                kt += BK;
+                if (kt >= k1) break;
+                rstep(kt, IC<1>{}, IC<0>{}, 0, -1, false);
+                kt += BK;
+                if constexpr (YIELD) {
+                    if (kt >= k1) break;
+                    rstep(kt, IC<0>{}, IC<0>{}, 0, -1, false);
+                    kt += BK;
+                    if (kt >= k1) break;
+                    rstep(kt, IC<1>{}, IC<0>{}, 0, -1, false);
+                    kt += BK;
+                }
+            }
+        } else {
         if constexpr (DMA) {
             if (lazyc) {          // first 2 FM FN / 2 k-steps, fully unrolled: chunk c = two accumulator tiles, fetched at step 2c,
                 double4_t creg[2];   // folded in at step 2c + 1 (16 VGPRs in flight; every accumulator index is a constant)
@@ -340,6 +521,8 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, int ti, int tj, lon
                     else kstep(kt, IC<0>{}, IC<0>{});
                     kt += BK;
                 }
+                // the end of the lazy-C prologue, kept in the spare LDS word behind the stage buffers until the stamps are derived
+                if (g.trace) smem[2 * STAGE] = __longlong_as_double((long long)wall_clock64());
             }
         }
         while (kt < k1) {                         // FN * FM is even: the stage parity is 0 here on both paths
@@ -357,11 +540,15 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, int ti, int tj, lon
                 kt += BK;
             }
         }
+        }
     }
 
     // (derived HERE, not ahead of the k-loop: two more live SGPRs in there and the LDS-DMA bases no longer fit the scalar file)
     long long* const trc = g.trace ? g.trace + 8L * wg : nullptr;   // workgroup-uniform; wg = the workgroup's number within ITS product
-    if (trc) trc[2] = (long long)wall_clock64();             // (every lane the same word: no divergent branch)
+    if (trc) {                                               // (every lane the same word: no divergent branch)
+        trc[2] = (long long)wall_clock64();
+        if constexpr (DMA) trc[1] = lazyc ? __double_as_longlong(smem[2 * STAGE]) : 0ll;   // behind k-step LZ: the lazy-C prologue is over
+    }
     // ---- epilogue: C = alpha * acc ---------------------------------------------------------
     if (!diag && (g.dbg & 512) && !(ldc & 1) && !((unsigned long)C & 15ul)) {
         // 16-byte stores: adjacent lanes (rows m, m+1) trade one value each by a DPP quad_perm, then the even lane stores

@@ -18,6 +18,9 @@ int pgp_test_gemm_shrink(pgp_ctx* ctx, const double* Y, int64_t ldy, int M, int 
 int pgp_test_gemm_zskip(pgp_ctx* ctx, int tile, int tri, int mask_diag, int zero_from, int zf_upper, double alpha, double beta,
                         const double* A, int64_t lda, const double* B, int64_t ldb, const double* Cin, double* C, int64_t ldc,
                         int M, int N, int K);
+/* two products in ONE launch (gemm_f64_pair_kernel): Ca = beta Ca + alpha A[:, :Ka] B[:, :Ka]', Cb the same with depth Kb */
+int pgp_test_gemm_pair(pgp_ctx* ctx, double alpha, double beta, const double* A, int64_t lda, const double* B, int64_t ldb, double* Ca,
+                       double* Cb, int64_t ldc, int M, int N, int Ka, int Kb);
 /* C -= A B' on the lower tiles (packed, masked diagonal tiles) but those whose first row and column lie in [skip_lo, skip_hi); with
    wait_ms > 0 every workgroup waits inside the kernel for a device counter that the second stream raises wait_ms later. */
 int pgp_test_gemm_skip_wait(pgp_ctx* ctx, int tile, const double* A, const double* B, double* C, int n, int K, int skip_lo,

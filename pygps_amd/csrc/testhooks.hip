@@ -402,6 +402,8 @@ int pgp_test_gemm(pgp_ctx* ctx, int tile, int a_kc, int b_kc, int tri, int mask_
                   int64_t ldc, int M, int N, int K, int iters, double* ms_out) {
     if (!ctx) return -1;
     pgp_ctx* c = ctx;
+    const bool poll = getenv("PGP_TEST_GEMM_YIELD") != nullptr;
+    if (poll && !c->yield_flags) return -2;          // (never a silent run of the kernels that do not poll)
     HIP_TRY(hipSetDevice(c->device));
     const size_t an = (size_t)lda * (a_kc ? M : K), bn = (size_t)ldb * (b_kc ? N : K), cn = (size_t)ldc * N;
     double *Ad, *Bd, *Cd;
@@ -412,8 +414,10 @@ int pgp_test_gemm(pgp_ctx* ctx, int tile, int a_kc, int b_kc, int tri, int mask_
     GemmArgs g{};
     g.A = Ad; g.lda = lda; g.a_kc = a_kc; g.B = Bd; g.ldb = ldb; g.b_kc = b_kc; g.C = Cd; g.ldc = ldc;
     g.M = M; g.N = N; g.K = K; g.alpha = alpha; g.beta = beta; g.tri = tri; g.tri_off = 0; g.mask_diag = mask_diag;
-    g.kmode = kmode; g.koff = koff; g.batch = 1; g.tile = tile; g.dbg = c->gemm_dbg;
+    g.kmode = kmode; g.koff = koff; g.batch = 1; g.tile = tile; g.dbg = c->gemm_dbg; g.ring = c->tile_ring != 0;
     if (getenv("PGP_TEST_GEMM_FOLD")) g.fold_rows = 1;                 // (tools: the two-tile-rows-per-workgroup kernel on the same arguments)
+    // (tests: the POLLING instantiations, as every bulk launch of a fit runs them -- the yield word is one more load in the ring's counts)
+    if (poll && gemm_f64_uses_dma(g)) { g.yield_flags = c->yield_flags; g.yield_role = 1; }
     hipStream_t ts = c->st;
     int rc = gemm_f64_launch(g, ts);
     HIP_TRY(hipStreamSynchronize(ts));
@@ -467,7 +471,7 @@ int pgp_test_gemm_trace(pgp_ctx* c, int M, int K, int tri, int warm, int conc, l
     HIP_TRY(hipMemset(Cd, 0, (size_t)M * M * 8)); HIP_TRY(hipMemset(C2, 0, (size_t)M * M * 8));
     GemmArgs g{};
     g.A = A; g.lda = M; g.B = A; g.ldb = M; g.C = Cd; g.ldc = M; g.M = M; g.N = M; g.K = K; g.alpha = -1.0; g.beta = 1.0;
-    g.tri = tri ? 2 : 0; g.mask_diag = tri ? 1 : 0; g.batch = 1; g.tile = 128; g.dbg = c->gemm_dbg;
+    g.tri = tri ? 2 : 0; g.mask_diag = tri ? 1 : 0; g.batch = 1; g.tile = 128; g.dbg = c->gemm_dbg; g.ring = c->tile_ring != 0;
     int rc = PGP_OK;
     for (int i = 0; i < warm && rc == PGP_OK; ++i) rc = gemm_f64_launch(g, c->st);
     HIP_TRY(hipStreamSynchronize(c->st));
@@ -514,7 +518,7 @@ int pgp_test_gemm_skip_wait(pgp_ctx* ctx, int tile, const double* A, const doubl
     HIP_TRY(hipMemset(fl, 0, 16));
     GemmArgs g{};
     g.A = Ad; g.lda = n; g.B = Bd; g.ldb = n; g.C = Cd; g.ldc = n; g.M = n; g.N = n; g.K = K; g.alpha = -1.0; g.beta = 1.0;
-    g.tri = 2; g.mask_diag = 1; g.batch = 1; g.tile = tile; g.dbg = c->gemm_dbg; g.skip_lo = skip_lo; g.skip_hi = skip_hi;
+    g.tri = 2; g.mask_diag = 1; g.batch = 1; g.tile = tile; g.dbg = c->gemm_dbg; g.ring = c->tile_ring != 0; g.skip_lo = skip_lo; g.skip_hi = skip_hi;
     if (wait_ms > 0) { g.wait_flag = fl; g.wait_target = 7u; g.wait_err = fl + 1; }
     int rc = gemm_f64_launch(g, c->st);
     if (rc == PGP_OK && wait_ms > 0) {
@@ -579,11 +583,39 @@ int pgp_test_gemm_zskip(pgp_ctx* ctx, int tile, int tri, int mask_diag, int zero
     GemmArgs g{};
     g.A = Ad; g.lda = lda; g.B = Bd; g.ldb = ldb; g.C = Cd; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.alpha = alpha; g.beta = beta;
     if (Ci) { g.Cin = Ci; g.ldcin = ldc; }
-    g.tri = tri; g.mask_diag = mask_diag; g.kmode = KM_FULL; g.batch = 1; g.tile = tile; g.dbg = c->gemm_dbg;
+    g.tri = tri; g.mask_diag = mask_diag; g.kmode = KM_FULL; g.batch = 1; g.tile = tile; g.dbg = c->gemm_dbg; g.ring = c->tile_ring != 0;
     g.zero_from = zero_from; g.zf_upper = zf_upper;
     const int rc = gemm_f64_launch(g, c->st);
     HIP_TRY(hipStreamSynchronize(c->st));
     if (rc == PGP_OK) HIP_TRY(hipMemcpy(C, Cd, cn, hipMemcpyDeviceToHost));
+    return rc;
+}
+
+// gemm_f64_pair_kernel (two products in one launch) on host buffers: Ca = beta Ca + alpha A[:, :Ka] B[:, :Ka]' and the same into Cb
+// with depth Kb, both M x N, plain rectangles of LDS-DMA 128-tiles.
+int pgp_test_gemm_pair(pgp_ctx* ctx, double alpha, double beta, const double* A, int64_t lda, const double* B, int64_t ldb, double* Ca,
+                       double* Cb, int64_t ldc, int M, int N, int Ka, int Kb) {
+    if (!ctx) return -1;
+    pgp_ctx* c = ctx;
+    const int K = std::max(Ka, Kb);
+    if (!A || !B || !Ca || !Cb || M <= 0 || N <= 0 || M % 128 || N % 128 || Ka <= 0 || Kb <= 0 || Ka % 16 || Kb % 16 || lda < M || ldb < N || ldc < M) return -2;
+    HIP_TRY(hipSetDevice(c->device));
+    DevScratch scr;
+    double *Ad = nullptr, *Bd = nullptr, *Cad = nullptr, *Cbd = nullptr;
+    const size_t an = (size_t)lda * K * 8, bn = (size_t)ldb * K * 8, cn = (size_t)ldc * N * 8;
+    CHK(scr.alloc(&Ad, an)); CHK(scr.alloc(&Bd, bn)); CHK(scr.alloc(&Cad, cn)); CHK(scr.alloc(&Cbd, cn));
+    HIP_TRY(hipMemcpy(Ad, A, an, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(Bd, B, bn, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(Cad, Ca, cn, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(Cbd, Cb, cn, hipMemcpyHostToDevice));
+    GemmArgs g{};
+    g.A = Ad; g.lda = lda; g.B = Bd; g.ldb = ldb; g.C = Cad; g.ldc = ldc; g.M = M; g.N = N; g.K = Ka; g.alpha = alpha; g.beta = beta;
+    g.kmode = KM_FULL; g.batch = 1; g.tile = 128; g.dbg = c->gemm_dbg; g.ring = c->tile_ring != 0;
+    GemmArgs h = g;
+    h.C = Cbd; h.K = Kb;
+    const int rc = gemm_f64_launch_pair(g, h, c->st);
+    HIP_TRY(hipStreamSynchronize(c->st));
+    if (rc == PGP_OK) { HIP_TRY(hipMemcpy(Ca, Cad, cn, hipMemcpyDeviceToHost)); HIP_TRY(hipMemcpy(Cb, Cbd, cn, hipMemcpyDeviceToHost)); }
     return rc;
 }
 
@@ -691,7 +723,7 @@ extern "C" int pgp_test_cumask_gemm(pgp_ctx* c, int M, int K, int reserve_per_xc
     HIP_TRY(hipMemset(A, 0, (size_t)M * K * 8)); HIP_TRY(hipMemset(Cm, 0, (size_t)M * M * 8));
     GemmArgs g{};
     g.A = A; g.lda = M; g.B = A; g.ldb = M; g.C = Cm; g.ldc = M; g.M = M; g.N = M; g.K = K;
-    g.alpha = -1.0; g.beta = 1.0; g.tile = 128; g.batch = 1; g.dbg = c->gemm_dbg;
+    g.alpha = -1.0; g.beta = 1.0; g.tile = 128; g.batch = 1; g.dbg = c->gemm_dbg; g.ring = c->tile_ring != 0;
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
     hipStream_t sts[2] = {ms, c->st};

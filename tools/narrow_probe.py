@@ -1,5 +1,6 @@
 """The bulk GEMM on a NARROW output (M x 512: the columns of one panel, one workgroup per CU) against the depth of K:
-what a left-looking update of one panel by all earlier ones would run at."""
+what a left-looking update of one panel by all earlier ones would run at.
+    python tools/narrow_probe.py [tile_ring]     (the staging ring of csrc/gemm_tile.h: 0 off, 1 on; default: the library's)"""
 import ctypes as C
 import os
 import sys
@@ -11,6 +12,8 @@ from pygps_amd import _lib
 
 lib = _lib.load()
 ctx = _lib.ctx()
+if len(sys.argv) > 1:
+    _lib.check(lib.pgp_set_option(ctx, b"tile_ring", int(sys.argv[1])))
 rng = np.random.RandomState(0)
 for M, N in ((8192, 512), (8192, 1024), (16384, 512)):
     for K in (512, 1024, 2048, 4096, 8192):

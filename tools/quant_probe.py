@@ -1,5 +1,6 @@
 """Round quantisation of the bulk GEMM: K = 512 launches whose tile counts straddle the 512 workgroup slots of the chip
-(2 per CU): time per launch against the number of 128 x 128 tiles."""
+(2 per CU): time per launch against the number of 128 x 128 tiles.
+    python tools/quant_probe.py [tile_ring]      (the staging ring of csrc/gemm_tile.h: 0 off, 1 on; default: the library's)"""
 import ctypes as C
 import os
 import sys
@@ -11,6 +12,8 @@ from pygps_amd import _lib
 
 lib = _lib.load()
 ctx = _lib.ctx()
+if len(sys.argv) > 1:
+    _lib.check(lib.pgp_set_option(ctx, b"tile_ring", int(sys.argv[1])))
 K = 512
 rng = np.random.RandomState(0)
 for mt, nt in ((12, 32), (16, 32), (17, 32), (20, 32), (24, 32), (28, 32), (32, 32), (33, 32), (40, 32), (48, 32), (64, 32)):

@@ -1,6 +1,6 @@
 """The rectangle TU_r of the sweep's trailing update (244 128 x 128 tiles at N = 8192: fewer than one per CU) alone on the chip,
 as 128 x 128 LDS-DMA tiles (one workgroup per CU) and as 128 x 64 ones (two per CU): ms per launch, warm.
-    python tools/tur_probe.py [M=7808] [N=512] [K=512]"""
+    python tools/tur_probe.py [M=7808] [N=512] [K=512] [ring=0|1]     (ring: option tile_ring, the staging ring of csrc/gemm_tile.h)"""
 import ctypes as C
 import os
 import sys
@@ -14,6 +14,8 @@ kv = dict(a.split("=") for a in sys.argv[1:])
 M, N, K = int(kv.get("M", 7808)), int(kv.get("N", 512)), int(kv.get("K", 512))
 lib = _lib.load()
 ctx = _lib.ctx()
+if "ring" in kv:
+    _lib.check(lib.pgp_set_option(ctx, b"tile_ring", int(kv["ring"])))
 rng = np.random.RandomState(0)
 A = np.asfortranarray(rng.randn(M, K) * 0.01)
 B = np.asfortranarray(rng.randn(N, K) * 0.01)
