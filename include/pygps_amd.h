@@ -114,6 +114,36 @@ int pgp_node_kernel(pgp_ctx* ctx, int kind, const double* A, int64_t n, double p
  * squared distances, the point itself left out, ties broken by the lower index, symmetrised with max (1 <= k < n). */
 int pgp_knn_graph(pgp_ctx* ctx, const double* pc, int64_t n, int64_t d, int k, double* A_out);
 
+/* ---- propagation kernels between graphs (GraphExtensions/graphKernels.py:27-184) -------------------------------
+ * n nodes in n_graphs graphs, k label classes (2 <= k <= PGP_PROP_MAX_LABELS).  All pointers are host memory.
+ *   indptr (n + 1), indices (nnz), vals (nnz): CSR of the matrix applied in the update (the row-normalised adjacency T, or
+ *       0.8 S for PGP_PROP_SPREAD), entries in the order they are to be summed; may be NULL for PGP_PROP_NONE.
+ *   lab_prob (n, k) row-major: the initial label distributions.  lab_orig (n, k) or NULL, push_back (n) or NULL: rows with
+ *       push_back[i] != 0 are read from lab_orig in every update ('label_propagation').
+ *   perm (n): the nodes in graph-grouped order; seg (n_graphs + 1): graph g owns perm[seg[g] .. seg[g + 1]).
+ *   V (h_max + 1, k) row-major and b (h_max + 1): projection and offset of every iteration; w > 0 the bin width.
+ *   update: PGP_PROP_NONE, PGP_PROP_T (lab <- T lab) or PGP_PROP_SPREAD (lab <- T lab + orig_weight lab_orig).
+ *   take_sqrt: lab <- sqrt(lab) in place before every hash (it carries into the next update, as in the reference).
+ *   sum: slice h is K_0 + ... + K_h, else K_h.
+ * K_out (n_graphs, n_graphs, h_max + 1) row-major; K_h[g1, g2] = number of node pairs (i in g1, j in g2) with
+ * floor((lab_i . v_h + b_h) / w) equal.  Counts are summed in 64-bit integers.  lab_out (n, k) or NULL: lab after the last
+ * iteration.  stage_ms_out (6) or NULL: device time of upload | update | hash | sort | gram | download in ms.
+ * Every product and sum runs in a defined order without contraction: the update in the stored CSR order, the hash over
+ * j = 0 .. k - 1.  Status: -1 ... -13 for the arguments in their order of mention (-6: CSR arrays missing or inconsistent,
+ * -9: perm is no permutation or seg does not partition it); PGP_ERR_PROP_NONFINITE: some key is not finite (overflow, or an
+ * infinite projection entry). */
+#define PGP_PROP_NONE 0
+#define PGP_PROP_T 1
+#define PGP_PROP_SPREAD 2
+#define PGP_PROP_MAX_LABELS 256
+#define PGP_PROP_SORT_LDS 2048  /* keys of one graph sorted in LDS; longer graphs sort on a global scratch */
+#define PGP_PROP_GRAM_LDS 5120  /* (key, count) pairs of the 32 graphs of a tile held in LDS; larger tiles read global memory */
+#define PGP_ERR_PROP_NONFINITE (-91)
+int pgp_propagation_kernel(pgp_ctx* ctx, int64_t n, int64_t k, int64_t n_graphs, const int64_t* indptr, const int32_t* indices,
+                           const double* vals, const double* lab_prob, const double* lab_orig, const uint8_t* push_back,
+                           const int32_t* perm, const int64_t* seg, int h_max, const double* V, const double* b, double w, int update,
+                           double orig_weight, int take_sqrt, int sum, double* K_out, double* lab_out, double* stage_ms_out);
+
 /* ---- data residency -------------------------------------------------------------------------
  * The optimiser calls the fit hundreds of times with identical (x, y) and only hyp changing
  * (Core/opt.py:70-75), so x and y are uploaded once.                                            */

@@ -25,6 +25,12 @@ PROG_MAX = 8                      # leaves / Scale nodes / products per device p
 MODE_TRAIN, MODE_CROSS, MODE_SELF_TEST = 0, 1, 2
 LIK_ERF, LIK_GAUSS, LIK_LAPLACE = 0, 1, 2
 ERR_LAPLACE_WNEG = -90
+ERR_PROP_NONFINITE = -91
+PROP_NONE, PROP_T, PROP_SPREAD = 0, 1, 2
+PROP_MAX_LABELS = 256             # label classes of pgp_propagation_kernel (include/pygps_amd.h)
+PROP_SORT_LDS = 2048              # keys of one graph sorted on chip; PROP_GRAM_LDS (key, count) pairs of a tile of 32 graphs held on chip
+PROP_GRAM_LDS = 5120
+PROP_STAGES = ("upload", "update", "hash", "sort", "gram", "download")
 FLAG_MATERN_REFERENCE_DER = 1
 STAGES = ("assemble", "potrf", "solve", "trtri", "lauum", "grad", "total")
 
@@ -46,6 +52,9 @@ SIGNATURES = {
     "pgp_set_pre": (C.c_int, [_vp, _dp, _i64, _dp, _i64]),
     "pgp_node_kernel": (C.c_int, [_vp, C.c_int, _dp, _i64, C.c_double, C.c_double, _dp]),
     "pgp_knn_graph": (C.c_int, [_vp, _dp, _i64, _i64, C.c_int, _dp]),
+    "pgp_propagation_kernel": (C.c_int, [_vp, _i64, _i64, _i64, C.POINTER(_i64), C.POINTER(C.c_int32), _dp, _dp, _dp,
+                                         C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(_i64), C.c_int, _dp, _dp, C.c_double,
+                                         C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp]),
     "pgp_set_data": (C.c_int, [_vp, _dp, _i64, _i64, _dp]),
     "pgp_exact_fit": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _dp, C.c_int,
                                 C.c_int, _dp, _dp, _dp, C.POINTER(_vp)]),
