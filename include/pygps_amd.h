@@ -50,7 +50,18 @@ typedef struct pgp_fitc pgp_fitc;     /* FITC posterior on the device (alpha, de
 #define PGP_COV_PRE 12    /* Core/cov.py:1429-1455 precomputed kernel matrix, no hypers: the value of element (row, col) is read from
                            * the matrices bound with pgp_set_pre.  Alone or as ONE leaf of a composite program (a second one: -13).
                            * Fits and pgp_predict only: pgp_cov answers -13 (the Python class slices its host arrays). */
-#define PGP_COV_NKIND 13
+/* Dot-product kernels, p = sum_k x_k z_k; J = 1e-10 on the training diagonal, 0 elsewhere.  k(x, x) differs from point to point:
+ * SELF_TEST writes one value per point, pgp_predict computes k(z, z) per test point on the device, EP reads K_ii off the matrix.
+ * The drivers built on one scalar k(x, x) -- pgp_fitc_* fits, pgp_sharded_exact_fit, pgp_gpmc_fit_predict -- answer -13 for these
+ * kinds and for programs that hold them. */
+#define PGP_COV_LINEAR 13 /* Core/cov.py:986-1024  hyp=[log sf]  sf2 (p + J), sf2 = exp(hyp0) (not squared, as the reference; derivative
+                           * 2 sf2 p).  Alone (any D) or as a leaf of a composite program. */
+#define PGP_COV_POLY 14   /* Core/cov.py:623-679   hyp=[log c, log sf], para=d >= 1 (else -12)  sf2 (c + p + J)^d, sf2 = exp(2 hyp1).
+                           * der 2 ("the degree") gives zeros on the plain kind.  Alone (any D) or as a leaf of a program. */
+#define PGP_COV_LINARD 15 /* Core/cov.py:1028-1074 hyp=[log ell_1..log ell_D]  sum_k x_k z_k / ell_k^2 + J (GPML covLINard; the reference
+                           * agrees at ell = 1).  Plain kind only, any D with nhyp <= 255 (1 / ell_k folded into the coordinates); as
+                           * a leaf of a composite program it answers -2. */
+#define PGP_COV_NKIND 16
 /* Sum / Product / Scale tree over primitives (Core/cov.py:230-328; up to two ARD leaves), registered with
  * pgp_set_composite and selected by kind = PGP_COV_COMPOSITE in pgp_cov / pgp_exact_fit / pgp_ep_fit.
  * hyp is the composite's flattened list in the reference's order (cov1.hyp + cov2.hyp; [scalar] + cov.hyp). */
@@ -88,7 +99,12 @@ int pgp_cov(pgp_ctx* ctx, int kind, int mode, int der, const double* x, int64_t 
  * nodes, 8 products after distributing products over sums; at most TWO ARD leaves (RBFard / RQard), each with D <= 64
  * (their 1 / ell_k^2 weights travel as kernel arguments); anything beyond returns -13 from the calls that use the program
  * -- the Python layer then takes the dense path (pgp_exact_fit_dense / pgp_ep_fit_dense).  The PLAIN kinds
- * PGP_COV_RBFARD / PGP_COV_RQARD take any D (the scales are folded into the coordinates). */
+ * PGP_COV_RBFARD / PGP_COV_RQARD take any D (the scales are folded into the coordinates).
+ * Budget of accumulators: beside the shared r^2 a program carries at most TWO more.  Every ARD leaf takes one; all PGP_COV_LINEAR /
+ * PGP_COV_POLY leaves together take one (the unweighted dot product, any D).  So: two ARD leaves, or one ARD leaf and any number of
+ * dot-product leaves; two ARD leaves and a dot-product leaf: -13.  A program holds either a PGP_COV_PRE leaf or dot-product leaves
+ * (both: -13).  Status of the calls that expand a program or a plain kind: -4 derivative index, -12 bad para (Poly d < 1),
+ * -13 over these limits. */
 int pgp_set_composite(pgp_ctx* ctx, const int32_t* prog, int nprog);
 
 /* cov.Pre: bind the precomputed matrices of the (one) PGP_COV_PRE leaf to the context; they stay resident until replaced.

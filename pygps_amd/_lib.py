@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("PYGPS_AMD_LIB") or os.path.join(_HERE, "libpygps_amd.
 COV_RBF, COV_RBFARD, COV_MATERN, COV_RBFUNIT, COV_RQ, COV_PIECEPOLY = 0, 1, 2, 3, 4, 5
 COV_RQARD, COV_GABOR, COV_PERIODIC, COV_NOISE, COV_CONST, COV_SM = 6, 7, 8, 9, 10, 11
 COV_PRE = 12                      # precomputed matrix (cov.Pre): a resident leaf of the device program, no hypers
+COV_LINEAR, COV_POLY, COV_LINARD = 13, 14, 15   # dot-product kernels: k(x, x) differs from point to point
 COV_COMPOSITE = 100
 PROG_LEAF, PROG_SUM, PROG_PRODUCT, PROG_SCALE = 1, 2, 3, 4
 PROG_MAX_ARD_DIM = 64             # input dimensions of the (single) ARD leaf of a device program

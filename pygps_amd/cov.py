@@ -81,10 +81,15 @@ class Kernel(object):
         ard = 1 if self._kind in (_lib.COV_RBFARD, _lib.COV_RQARD) else 0
         if ard and len(self.hyp) - (1 if self._kind == _lib.COV_RBFARD else 2) > _lib.PROG_MAX_ARD_DIM:
             return None
-        return [_lib.PROG_LEAF, int(kind), int(para), int(flags), int(h0)], 1, 1, ard * 1000
+        dot = 1 if self._kind in (_lib.COV_LINEAR, _lib.COV_POLY) else 0
+        return [_lib.PROG_LEAF, int(kind), int(para), int(flags), int(h0)], 1, 1, ard * 1000 + dot * 100000
 
     def _pre_leaves(self):
         """The cov.Pre leaves of this (sub)tree."""
+        return []
+
+    def _dot_leaves(self):
+        """The dot-product leaves (Linear, Poly, LINard) of this (sub)tree: k(x, x) differs from point to point."""
         return []
 
     def _on_device(self):
@@ -318,6 +323,103 @@ class Const(_DeviceKernel):
     def __init__(self, log_sigma=0.):
         self.hyp = [log_sigma]
         self.para = []
+
+
+class _DotKernel(_DeviceKernel):
+    """Kernels of the dot product p = sum_k x_k z_k.  Not functions of a distance: their diagonal and k(z, z) differ from point to
+    point, so 'self_test' is a genuine vector, predict takes k(z, z) per test point and EP reads K_ii off the assembled matrix
+    (csrc/sqdist_tile.h CovSpec::diag_per_point).  FITC, sharded fits and GPMC's shared route assume one scalar k(x, x) and refuse
+    them (``refuse_dot``)."""
+
+    def _dot_leaves(self):
+        return [self]
+
+    def _n_der(self, x, z):
+        return len(self.hyp)
+
+    def getDerMatrix(self, x=None, z=None, mode=None, der=None):
+        self.checkInputGetDerMatrix(x, z, mode, der)
+        if der >= self._n_der(x, z):                     # on the host, before any device call
+            raise Exception(self._WRONG_DER)
+        self._device_params()
+        return self._device_eval(x, z, mode, der)
+
+    def getCovMatrix(self, x=None, z=None, mode=None):
+        self.checkInputGetCovMatrix(x, z, mode)
+        self._device_params()
+        return self._device_eval(x, z, mode, None)
+
+
+class Linear(_DotKernel):
+    """Linear kernel sf2 (x . z).  hyp = [log_sigma]   (Core/cov.py:986-1024).  As in the reference -- and like ``Const`` -- the
+    variance is exp(log_sigma) (:997, not squared), the training matrix carries a 1e-10 diagonal jitter (:1003) and the derivative
+    is 2 sf2 (x . z) (:1021; the reference's 1e-16 on its diagonal is dropped).  A leaf of device programs; alone it runs as a
+    one-leaf program, for any input dimension."""
+    _kind = _lib.COV_LINEAR
+    _WRONG_DER = "Wrong derivative index in covLinear"
+
+    def __init__(self, log_sigma=0.):
+        self.hyp = [log_sigma]
+        self.para = []
+
+
+class Poly(_DotKernel):
+    """Polynomial kernel sf2 (c + x . z)^d.  hyp = [log_c, log_sigma], para = [d], integer d >= 1   (Core/cov.py:623-679).
+    c = exp(log_c), sf2 = exp(2 log_sigma); 1e-10 diagonal jitter inside the power on 'train' (:649).  ``getDerMatrix(der=2)``
+    ("the degree") returns zeros (:675-676).  A leaf of device programs, any input dimension."""
+    _kind = _lib.COV_POLY
+    _WRONG_DER = "Wrong derivative entry in Poly"
+    _BAD_PARA = "Poly needs an integer degree d >= 1"
+
+    def __init__(self, log_c=0., d=2, log_sigma=0.):
+        self.hyp = [log_c, log_sigma]
+        self.para = [d]
+
+    def _n_der(self, x, z):
+        return 3
+
+    def _device_params(self):
+        d = self.para[0]
+        if np.abs(d - np.round(d)) < 1e-8:             # Core/cov.py:640-643
+            d = int(round(d))
+        assert d >= 1.
+        return self._kind, int(d), 0
+
+
+class LINard(_DotKernel):
+    """Linear kernel with ARD: sum_k x_k z_k / ell_k^2 (GPML covLINard), 1e-10 diagonal jitter on 'train'.  hyp = log_ell_list
+    (Core/cov.py:1028-1074).  Derivative w.r.t. log ell_k: -2 x_k z_k / ell_k^2.
+
+    Deviation from the reference, which ignores ell on 'train' and 'self_test' and divides by ell once on 'cross' (:1047-1053), so
+    that its derivatives do not differentiate its own value; the two agree in every mode at ell = 1, the default hypers.  There is no
+    ``reference_compat`` for it.
+
+    Alone it runs on the device with 1 / ell_k folded into the coordinates, for any D with at most 255 hypers.  Not a leaf of a
+    device program: trees that contain it combine the children's device-built matrices and fit through the dense route."""
+    _kind = _lib.COV_LINARD
+    _WRONG_DER = "Wrong derivative index in covLINard"
+    _OVER_LIMIT = "pygps_amd: cov.LINard runs on the device for at most 255 length-scales; there is no CPU fallback"
+
+    def __init__(self, D=None, log_ell_list=None):
+        if log_ell_list is None:
+            self.hyp = [0. for _ in range(D)]
+        else:
+            self.hyp = log_ell_list
+        self.para = []
+
+    def _n_der(self, x, z):
+        ref = x if x is not None else z
+        return np.shape(ref)[1]                           # Core/cov.py:1063: der < D
+
+    def _program(self, h0):
+        return None                                       # its length-scales live in the coordinates of a one-leaf program
+
+
+def refuse_dot(covfunc, what):
+    """FITC and sharded fits assume one scalar k(x, x) for all points; dot-product kernels have none."""
+    if isinstance(covfunc, Kernel) and covfunc._dot_leaves():
+        raise NotImplementedError("pygps_amd: the dot-product kernels (cov.Linear, cov.Poly, cov.LINard) cannot be used with %s: "
+                                  "their k(x, x) differs from point to point" % what)
 
 
 class SM(Kernel):
@@ -564,17 +666,24 @@ def refuse_pre(covfunc, what):
 # A tree whose leaves all have isotropic device functors is evaluated in ONE pass of the tile kernel as a device
 # program (sum of products of leaf functors, csrc/sqdist_tile.h CovProgram) -- in getCovMatrix/getDerMatrix and,
 # more importantly, inside Exact/EP fits and predict.  Up to TWO leaves may be ARD kernels (RBFard / RQard, D <= 64): each
-# gets its own weighted distance, accumulated beside the shared one.  Trees with three ARD leaves (or more than 8 leaves /
+# gets its own weighted distance, accumulated beside the shared one.  Linear / Poly leaves share ONE further accumulator, the
+# dot product (any D), which counts against the same budget of two.  Trees with three ARD leaves (or more than 8 leaves /
 # products) still offer getCovMatrix/getDerMatrix by combining the children's device-built matrices.
 class _Composite(Kernel):
     _kind = _lib.COV_COMPOSITE
 
     def _tokens(self):
         pr = self._program(0)
-        if pr is None or pr[1] > _lib.PROG_MAX or pr[2] > _lib.PROG_MAX or pr[3] % 1000 > _lib.PROG_MAX or pr[3] >= 3000:
-            return None                                   # too many leaves / products / Scale nodes, or more than two ARD leaves
+        if pr is None or pr[1] > _lib.PROG_MAX or pr[2] > _lib.PROG_MAX or pr[3] % 1000 > _lib.PROG_MAX:
+            return None                                   # too many leaves / products / Scale nodes
+        # beside the shared r^2 a program carries at most two more accumulators: one per ARD leaf, one for ALL Linear / Poly leaves
+        n_ard, n_dot = pr[3] % 100000 // 1000, pr[3] // 100000
+        if n_ard + (1 if n_dot else 0) > 2:
+            return None
         if len(self._pre_leaves()) > 1:
             return None                                   # more than one cov.Pre leaf
+        if n_dot and self._pre_leaves():
+            return None                                   # the Pre tile and the dot product do not share a program
         return pr[0]
 
     def _bind(self, ctx):
@@ -633,13 +742,16 @@ class _Pair(_Composite):
     def _pre_leaves(self):
         return self.cov1._pre_leaves() + self.cov2._pre_leaves()
 
+    def _dot_leaves(self):
+        return self.cov1._dot_leaves() + self.cov2._dot_leaves()
+
     def _program(self, h0):
         a = self.cov1._program(h0)
         b = self.cov2._program(h0 + len(self.cov1.hyp))
         if a is None or b is None:
             return None
         nprod = a[2] + b[2] if self._op == _lib.PROG_SUM else a[2] * b[2]
-        return a[0] + b[0] + [self._op], a[1] + b[1], nprod, a[3] + b[3]     # [3]: Scale nodes + 1000 per ARD leaf
+        return a[0] + b[0] + [self._op], a[1] + b[1], nprod, a[3] + b[3]     # [3]: Scale nodes + 1000 per ARD leaf + 100000 per dot leaf
 
 
 class SumOfKernel(_Pair):
@@ -695,6 +807,9 @@ class ScaleOfKernel(_Composite):
     def _pre_leaves(self):
         return self.cov._pre_leaves()
 
+    def _dot_leaves(self):
+        return self.cov._dot_leaves()
+
     def _program(self, h0):
         a = self.cov._program(h0 + 1)
         if a is None:
@@ -717,6 +832,7 @@ class FITCOfKernel(Kernel):
 
     def __init__(self, cov, inducingInput):
         refuse_pre(cov, "the FITC approximation (fitc(u) of a precomputed matrix has no meaning)")
+        refuse_dot(cov, "the FITC approximation")
         self.inducingInput = np.asarray(inducingInput, dtype=float)
         self.covfunc = cov
         self.para = []

@@ -99,6 +99,11 @@ __device__ __forceinline__ const double* prog_der_w(const CovProgram& P) { retur
 __device__ __forceinline__ const double* prog_der_w(const CovParams&) { return nullptr; }
 __device__ __forceinline__ double prog_elem(const CovProgram& P, double s, double dk2, bool same, double s1, double s2, double pv) { return cov_elem(P, s, dk2, same, s1, s2, pv); }
 __device__ __forceinline__ double prog_elem(const CovParams& p, double s, double dk2, bool same, double, double, double) { return cov_elem(p, s, dk2, same); }
+// the DOT instantiations: the element's dot product pd beside the distances
+__device__ __forceinline__ double prog_elem_dot(const CovProgram& P, double s, double dk2, bool same, double s1, double pd) { return cov_elem<true>(P, s, dk2, same, s1, 0.0, 0.0, pd); }
+__device__ __forceinline__ double prog_elem_dot(const CovParams&, double, double, bool, double, double) { return 0.0; }
+__device__ __forceinline__ int prog_dot_der(const CovProgram& P) { return cov_dot_der(P); }
+__device__ __forceinline__ int prog_dot_der(const CovParams&) { return -1; }
 __device__ __forceinline__ const double* prog_pre(const CovProgram& P) { return P.pre; }
 __device__ __forceinline__ const double* prog_pre(const CovParams&) { return nullptr; }
 __device__ __forceinline__ long prog_pre_ld(const CovProgram& P) { return P.pre_ld; }
@@ -192,6 +197,38 @@ __device__ __forceinline__ void slab_accum3(const double* __restrict__ smx, doub
     }
 }
 
+// programs with dot-product leaves: pd += a_k b_k (fma, coordinate order) beside r^2 and, when ARD, the ARD leaf's weighted distance
+template <bool ARD>
+__device__ __forceinline__ void slab_accum_dot(const double* __restrict__ smx, double (&s)[4][4], double (&s1)[ARD ? 4 : 1][4],
+                                               double (&pd)[4][4], const double* __restrict__ w, int k0) {
+    const int t = threadIdx.x, tr = t >> 4, tc = t & 15;
+    const double* xr = smx;
+    const double* xc = smx + SKC * ST;
+#pragma unroll
+    for (int k = 0; k < SKC; ++k) {
+        double wk = 0.0;
+        if (ARD) wk = (k0 + k) < CP_MAXARD ? w[k0 + k] : 0.0;
+        const double2_t r01 = *(const double2_t*)(xr + k * ST + 4 * tr);
+        const double2_t r23 = *(const double2_t*)(xr + k * ST + 4 * tr + 2);
+        const double2_t c01 = *(const double2_t*)(xc + k * ST + 2 * tc);
+        const double2_t c23 = *(const double2_t*)(xc + k * ST + 2 * tc + 32);
+        const double rv[4] = {r01[0], r01[1], r23[0], r23[1]};
+        const double cv[4] = {c01[0], c01[1], c23[0], c23[1]};
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const double df = rv[a] - cv[b];
+                if (ARD) {
+                    const double d2 = df * df;
+                    s[a][b] += d2;
+                    s1[a][b] = fma(wk, d2, s1[a][b]);
+                } else s[a][b] = fma(df, df, s[a][b]);
+                pd[a][b] = fma(rv[a], cv[b], pd[a][b]);
+            }
+    }
+}
+
 __device__ __forceinline__ void slab_accum(const double* __restrict__ smx, double (&s)[4][4]) {
     const int t = threadIdx.x, tr = t >> 4, tc = t & 15;
     const double* xr = smx;
@@ -244,6 +281,8 @@ __global__ __launch_bounds__(256) void cov_tile_kernel(const double* __restrict_
     constexpr bool PARD = PROG && (KIND & 3) >= 1;  // program with an ARD leaf: second (weighted) distance
     constexpr bool PARD2 = PROG && (KIND & 3) == 2; // two ARD leaves: a third distance, kept in registers
     constexpr bool PPRE = PROG && (KIND & 4) != 0;  // program with a precomputed-matrix leaf: its tile is loaded beside the distances
+    constexpr bool PDOT = PROG && (KIND & 8) != 0;  // program with dot-product leaves (Linear / Poly / plain LINard): sum_k x_k z_k beside
+                                                    // the distances, kept in registers; KIND 8 (no ARD leaf) and 9 (one) exist
     constexpr int SMT = PARD ? 2 * 16 * 256 : (MODE == MODE_SYM ? ST * TS : (PROG ? 16 * 256 : 2));
     // coordinate slabs (2 x 16 x 64 doubles) and the mirror-transpose tile share one region: 33.8 KB -> 4 WGs per CU
     constexpr int SMX = 2 * SKC * ST;
@@ -273,13 +312,19 @@ __global__ __launch_bounds__(256) void cov_tile_kernel(const double* __restrict_
         for (int a = 0; a < 4; ++a)
 #pragma unroll
             for (int b = 0; b < 4; ++b) { s[a][b] = 0.0; if (PARD) s1[a][b] = 0.0; if (PARD2) s2[a][b] = 0.0; }
+        double pd[PDOT ? 4 : 1][4];
+        if constexpr (PDOT) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) pd[e >> 2][e & 3] = 0.0;
+        }
         if constexpr (SMK) {
 #pragma unroll 1
             for (int e = 0; e < 16; ++e) {
                 const int rl = 4 * tr + (e >> 2), cl = 2 * tc + (e & 1) + 32 * ((e >> 1) & 1);
                 put16(s, e, sm_elem(cp, smx + rl, smx + SKC * ST + cl));
             }
-        } else if constexpr (PARD2) slab_accum3(smx, s, s1, s2, prog_ardw(cp), prog_ardw2(cp), 0);
+        } else if constexpr (PDOT) slab_accum_dot<PARD>(smx, s, s1, pd, prog_ardw(cp), 0);
+        else if constexpr (PARD2) slab_accum3(smx, s, s1, s2, prog_ardw(cp), prog_ardw2(cp), 0);
         else if constexpr (PARD) slab_accum2(smx, s, s1, prog_ardw(cp), 0); else slab_accum(smx, s);
         for (int k0 = SKC; !SMK && k0 < dpad; k0 += SKC) {  // d > 16: further slabs, loaded in place
             SlabRegs h;
@@ -287,7 +332,8 @@ __global__ __launch_bounds__(256) void cov_tile_kernel(const double* __restrict_
             __syncthreads();
             slab_stage(smx, h);
             __syncthreads();
-            if constexpr (PARD2) slab_accum3(smx, s, s1, s2, prog_ardw(cp), prog_ardw2(cp), k0);
+            if constexpr (PDOT) slab_accum_dot<PARD>(smx, s, s1, pd, prog_ardw(cp), k0);
+            else if constexpr (PARD2) slab_accum3(smx, s, s1, s2, prog_ardw(cp), prog_ardw2(cp), k0);
             else if constexpr (PARD) slab_accum2(smx, s, s1, prog_ardw(cp), k0); else slab_accum(smx, s);
         }
 
@@ -301,6 +347,8 @@ __global__ __launch_bounds__(256) void cov_tile_kernel(const double* __restrict_
             const int pder = cov_ard_der(cp);           // derivative w.r.t. an ARD length-scale of the program's ARD leaf
             double pm[PPRE ? 4 : 1][4];
             if constexpr (PPRE) pre_tile_load(prog_pre(cp), prog_pre_ld(cp), r0, c0, pm);
+            int ddk = -1;                               // plain LINard: the coordinate of the length-scale the derivative is taken in
+            if constexpr (PDOT) ddk = prog_dot_der(cp);
 #pragma unroll 1
             for (int e = 0; e < 16; ++e) {
                 const int a = e >> 2, b = e & 3;
@@ -315,6 +363,10 @@ __global__ __launch_bounds__(256) void cov_tile_kernel(const double* __restrict_
                 if constexpr (PARD2) s2e = sel16(s2, e);
                 double pve = 0.0;
                 if constexpr (PPRE) pve = sel16(pm, e);
+                if constexpr (PDOT) {
+                    if (ddk >= 0) dk2 = XrT[(long)ddk * ldr + r] * XcT[(long)ddk * ldc + c];
+                    sv[e * 256] = prog_elem_dot(cp, sv[e * 256], dk2, MODE != MODE_RECT && r == c, PARD ? sv1[e * 256] : 0.0, sel16(pd, e));
+                } else
                 sv[e * 256] = prog_elem(cp, sv[e * 256], dk2, MODE != MODE_RECT && r == c, PARD ? sv1[e * 256] : 0.0, s2e, pve);
             }
 #pragma unroll
@@ -904,6 +956,14 @@ static int cov_tile_dispatch(const CovSpec& cs, int train, long ntr, long ntc_, 
                                          XcT, ldc, m, dpad, pg, inv_sn2, out, ldo, tiles, ntiles, nt_)
             if (pg.ard_leaf2 >= 0) PRE_LAUNCH(6); else if (pg.ard_leaf >= 0) PRE_LAUNCH(5); else PRE_LAUNCH(4);
 #undef PRE_LAUNCH
+        } else if (pg.dot_mask) {
+            if (pg.ard_leaf2 >= 0) return -13;        // the dot product is the second extra accumulator (make_spec refuses this too)
+            if (pg.ard_leaf >= 0)
+                hipLaunchKernelGGL((cov_tile_kernel<MODE, CovProgram, 9, false, false>), dim3(nblk), dim3(256), 0, st, XrT, ldr, n,
+                                   XcT, ldc, m, dpad, pg, inv_sn2, out, ldo, tiles, ntiles, nt_);
+            else
+                hipLaunchKernelGGL((cov_tile_kernel<MODE, CovProgram, 8, false, false>), dim3(nblk), dim3(256), 0, st, XrT, ldr, n,
+                                   XcT, ldc, m, dpad, pg, inv_sn2, out, ldo, tiles, ntiles, nt_);
         } else if (pg.ard_leaf2 >= 0)
             hipLaunchKernelGGL((cov_tile_kernel<MODE, CovProgram, 2, false, false>), dim3(nblk), dim3(256), 0, st, XrT, ldr, n,
                                XcT, ldc, m, dpad, pg, inv_sn2, out, ldo, tiles, ntiles, nt_);
@@ -1037,11 +1097,24 @@ __global__ void cov_self_kernel(COV cp, int same, double* out) {
 // Programs with a precomputed-matrix leaf: the diagonal differs from point to point.  out[j] = k_jj with the leaf's value
 // pre[j * stride] (train = 1: diag(M2), stride ld + 1; train = 2: the last row of M1, 'self_test');
 // sub: out[j] = max(k_jj - out[j], 0) -- the predictive variance from the column sums of squares already in out.
+// Programs with dot-product leaves (DOT): k_jj from |x_j|^2 = sum_k x_jk^2 of the point's own coordinates XT[k * ld + j] (k-major,
+// dpad rows, zero-padded), summed by fma in coordinate order like the tiles' dot product; pre is not read.  With a derivative
+// selected (P.der >= 0) out[j] is that derivative's k_jj.
+template <bool DOT>
 __global__ __launch_bounds__(256) void cov_self_vec_kernel(CovProgram P, int same, const double* __restrict__ pre, long stride,
-                                                           long m, double* __restrict__ out, int sub) {
+                                                           long m, double* __restrict__ out, int sub,
+                                                           const double* __restrict__ XT, long ld, int dpad) {
     const long j = (long)blockIdx.x * 256 + threadIdx.x;
     if (j >= m) return;
-    const double k = cov_elem(P, 0.0, 0.0, same != 0, 0.0, 0.0, pre[j * stride]);
+    double k;
+    if constexpr (DOT) {
+        double pd = 0.0;
+        for (int q = 0; q < dpad; ++q) { const double v = XT[(long)q * ld + j]; pd = fma(v, v, pd); }
+        const int ddk = cov_dot_der(P);
+        double dk = 0.0;
+        if (ddk >= 0) { const double v = XT[(long)ddk * ld + j]; dk = v * v; }
+        k = cov_elem<true>(P, 0.0, dk, same != 0, 0.0, 0.0, 0.0, pd);
+    } else k = cov_elem(P, 0.0, 0.0, same != 0, 0.0, 0.0, pre[j * stride]);
     out[j] = sub ? fmax(k - out[j], 0.0) : k;
 }
 int cov_self_vec_launch(const CovSpec& cs, int train, const double* pre, long stride, long m, double* out_dev, int sub,
@@ -1050,8 +1123,19 @@ int cov_self_vec_launch(const CovSpec& cs, int train, const double* pre, long st
     if (m <= 0) return PGP_OK;
     CovProgram pg = cs.pg;
     for (int l = 0; l < pg.nleaf; ++l) pg.leaf[l].train = train;
-    hipLaunchKernelGGL(cov_self_vec_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, pg, train == 1, pre, stride, m,
-                       out_dev, sub);
+    hipLaunchKernelGGL(cov_self_vec_kernel<false>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, pg, train == 1, pre, stride, m,
+                       out_dev, sub, (const double*)nullptr, 0L, 0);
+    return hipGetLastError() == hipSuccess ? PGP_OK : PGP_ERR_HIP;
+}
+// XT: the m points' scaled, transposed coordinates (dpad x ld, ld >= m)
+int cov_self_dot_launch(const CovSpec& cs, int train, const double* XT, long ld, int dpad, long m, double* out_dev, int sub,
+                        hipStream_t st) {
+    if (!cs.has_dot() || cs.has_pre() || !XT || ld < m) return -14;
+    if (m <= 0) return PGP_OK;
+    CovProgram pg = cs.pg;
+    for (int l = 0; l < pg.nleaf; ++l) pg.leaf[l].train = train;
+    hipLaunchKernelGGL(cov_self_vec_kernel<true>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, pg, train == 1,
+                       (const double*)nullptr, 0L, m, out_dev, sub, XT, ld, dpad);
     return hipGetLastError() == hipSuccess ? PGP_OK : PGP_ERR_HIP;
 }
 

@@ -302,6 +302,9 @@ static int leaf_nhyp(int kind, long d) {
         case PGP_COV_RBFUNIT: case PGP_COV_NOISE: case PGP_COV_CONST: return 1;
         case PGP_COV_RQ: case PGP_COV_PERIODIC: return 3;
         case PGP_COV_PRE: return 0;
+        case PGP_COV_LINEAR: return 1;
+        case PGP_COV_POLY: return 2;
+        case PGP_COV_LINARD: return (int)d;
         default: return -1;
     }
 }
@@ -341,6 +344,13 @@ static int make_leaf(int kind, const double* hyp, int nhyp, int para, int flags,
             break;
         case PGP_COV_NOISE: cp.sf2 = exp(2.0 * hyp[0]); break;                   // cov.py:1268
         case PGP_COV_CONST: cp.sf2 = exp(hyp[0]); break;                         // cov.py:951 (not squared)
+        // dot-product kernels (sqdist_tile.h dot_value): functions of sum_k x_k z_k, no iso
+        case PGP_COV_LINEAR: cp.sf2 = exp(hyp[0]); break;                        // cov.py:997 (not squared)
+        case PGP_COV_POLY:
+            if (para < 1) return -12;                                            // cov.py:642 assert
+            cp.alpha = exp(hyp[0]); cp.sf2 = exp(2.0 * hyp[1]); cp.md = para;    // c, sf2, the degree (cov.py:637-643)
+            break;
+        case PGP_COV_LINARD: break;                                              // 1 / ell_k folded into the coordinates (make_spec)
     }
     return PGP_OK;
 }
@@ -388,12 +398,18 @@ int make_spec(pgp_ctx* c, int kind, const double* hyp, int nhyp, int para, int f
         P = CovProgram{};
         double iso;
         CHK(make_leaf(kind, hyp, nhyp, para, flags, d, P.leaf[0], iso));
-        if (der >= nhyp) return -4;
+        // Poly accepts der == 2 ("derivative w.r.t. the degree" = zeros, cov.py:675-676)
+        const int nder = kind == PGP_COV_POLY ? 3 : nhyp;
+        if (der >= nder) return -4;
+        if (kind == PGP_COV_LINARD && nhyp > 255) return -13;
         P.nleaf = 1; P.nterm = 1; P.nscale = 0; P.is2[0] = iso * iso; P.hyp0[0] = 0; P.nh[0] = nhyp; P.ard_leaf = -1; P.ard_leaf2 = -1;
         P.pre_leaf = kind == PGP_COV_PRE ? 0 : -1;
+        P.dot_mask = (kind == PGP_COV_LINEAR || kind == PGP_COV_POLY || kind == PGP_COV_LINARD) ? 1u : 0u;
         P.coef[0] = 1.0; P.tl[0] = 1u; P.ts[0] = 0u;
         P.der = der; P.der_leaf = der >= 0 ? 0 : -1; P.der_j = der; P.der_scale = -1;
-        cs.prog = true; cs.scale.assign(d, 1.0); cs.ncov = nhyp; cs.nder = nhyp;
+        cs.prog = true; cs.scale.assign(d, 1.0); cs.ncov = nhyp; cs.nder = nder;
+        if (kind == PGP_COV_LINARD)                                              // x_k / ell_k, as plain RBFard folds its scales
+            for (long k = 0; k < d; ++k) cs.scale[k] = 1.0 / exp(hyp[k]);
         return bind_pre(c, cs);
     }
     if (kind != PGP_COV_COMPOSITE) {
@@ -436,6 +452,9 @@ int make_spec(pgp_ctx* c, int kind, const double* hyp, int nhyp, int para, int f
             i += 5;
             const bool ard = lk == PGP_COV_RBFARD || lk == PGP_COV_RQARD;
             if (ard && (P.ard_leaf2 >= 0 || d > CP_MAXARD)) return -13;           // at most two ARD leaves (own weighted distances), D <= 64
+            if (lk == PGP_COV_LINARD) return -2;                                  // plain kind only: its scales live in the coordinates
+            const bool dot = lk == PGP_COV_LINEAR || lk == PGP_COV_POLY;
+            if (dot) P.dot_mask |= 1u << P.nleaf;
             const int nh = leaf_nhyp(lk, d);
             if (nh < 0) return -2;
             if (h0 < 0 || h0 + nh > nhyp) return -11;
@@ -482,6 +501,8 @@ int make_spec(pgp_ctx* c, int kind, const double* hyp, int nhyp, int para, int f
         }
     }
     if (stack.size() != 1 || used != nhyp) return -11;
+    // beside r^2 at most two more accumulators: one per ARD leaf, one for all dot-product leaves; and no Pre tile beside the dot product
+    if (P.dot_mask && (P.ard_leaf2 >= 0 || P.pre_leaf >= 0)) return -13;
     P.nterm = (int)stack[0].size();
     for (int t = 0; t < P.nterm; ++t) {
         P.tl[t] = stack[0][t].leaves; P.ts[t] = stack[0][t].scales;
@@ -509,6 +530,10 @@ int cov_point_value(pgp_ctx* c, const CovSpec& cs, int train, double* out) {
     // a cov.Pre leaf: K_ii and k(z,z) are vectors.  The fits read the training diagonal off the assembled K, pgp_predict takes
     // k(z,z) from the last row of the bound M1 (cov_self_vec_launch); the one number is not used
     if (cs.has_pre()) { *out = 0.0; return PGP_OK; }
+    // dot-product leaves have no such scalar either, and nobody may ask for one: the exact, EP and Laplace fits skip the call,
+    // pgp_cov and pgp_predict take the per-point vector (cov_self_dot_launch); the drivers built on one k(x, x) for all points
+    // (FITC, the sharded fit, GPMC's shared engine) end here
+    if (cs.has_dot()) return -13;
     if (!cs.prog && cs.cp.der < 0) {          // every functor primitive has k(x,x) = sf2 (RBFunit: sf2 = 1)
         (void)train;
         *out = cs.cp.sf2;
@@ -973,7 +998,7 @@ int pgp_exact_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para
     const std::vector<double>& sc = cp.scale;
     CHK(ensure_workspace(c, np));
     double kss = 0.0;
-    if (factor_out) CHK(cov_point_value(c, cp, 2, &kss));
+    if (factor_out && !cp.has_dot()) CHK(cov_point_value(c, cp, 2, &kss));      // (dot-product leaves: predict takes k(z,z) per point)
     const long need = std::max(hadamard_partial_count(np, ncov), 32L * np);       // also the partials of upper_matvec
     if ((want >= 3 || fused) && c->partial_cap < need) {
         if (c->partial) (void)hipFree(c->partial);
@@ -1161,6 +1186,24 @@ int pgp_cov(pgp_ctx* c, int kind, int mode, int der, const double* x, int64_t n,
     CovSpec cp;
     CHK(make_spec(c, kind, hyp, nhyp, para, flags, der, d, cp));
     if (cp.has_pre()) return -13;                    // cov.Pre: getCovMatrix / getDerMatrix are host slices and sums (pygps_amd/cov.py)
+    if (mode == PGP_MODE_SELF_TEST && cp.diag_per_point()) {
+        // dot-product leaves: k(z_j, z_j) (or the selected derivative of it) differs from point to point -- one value per point from
+        // the point's own coordinates (Core/cov.py:644-646, 998-1000)
+        const int dpad = (int)round_up(d, SKC);
+        const long ldc = round_up(m, 128);
+        PoolScratch tmp(c);
+        double *zd = nullptr, *XcT = nullptr, *scd = nullptr, *od = nullptr;
+        CHK(tmp.alloc(&zd, m * d * sizeof(double)));
+        CHK(tmp.alloc(&XcT, (size_t)dpad * ldc * sizeof(double)));
+        CHK(tmp.alloc(&scd, dpad * sizeof(double)));
+        CHK(tmp.alloc(&od, m * sizeof(double)));
+        HIP_TRY(hipMemcpyAsync(zd, z, m * d * sizeof(double), hipMemcpyHostToDevice, st));
+        CHK(upload_scaled(c, zd, m, d, cp.scale, XcT, ldc, dpad, scd));
+        CHK(cov_self_dot_launch(cp, 2, XcT, ldc, dpad, m, od, 0, st));
+        HIP_TRY(hipMemcpyAsync(out, od, m * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return PGP_OK;
+    }
     if (mode == PGP_MODE_SELF_TEST) {
         // zero distance: the functor itself gives value and derivatives (Core/cov.py:815-817, 924-925, 1163-1177,
         // SURVEY Q6), including the Matern derivative quirk and Noise = 0 on 'self_test' (cov.py:1271)

@@ -1176,8 +1176,9 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
     CHK(ensure_workspace(c, np));
     double kdiag = 0.0;                               // K_ii, identical for every training point (stationary kernels)
     double kss = 0.0;
-    const bool vdiag = dense || cp.has_pre();         // K_ii differs from point to point: read off the assembled K (a cov.Pre leaf: diag(M2))
-    if (!dense) {
+    const bool vdiag = dense || cp.diag_per_point();  // K_ii differs from point to point: read off the assembled K (a cov.Pre leaf: diag(M2);
+                                                      // dot-product leaves: sf2 |x_i|^2 and the like)
+    if (!dense && !cp.has_dot()) {                    // (vdiag: kdiag is not read; kss is only stored for predict)
         CHK(cov_point_value(c, cp, 1, &kdiag));
         CHK(cov_point_value(c, cp, 2, &kss));
     }

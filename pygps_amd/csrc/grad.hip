@@ -558,6 +558,32 @@ __global__ __launch_bounds__(256) void point_norm_kernel(const double* __restric
     nrm[p] = s;
 }
 
+// Plain LINard, K = sum_k xs_k zs_k + J on coordinates scaled by 1 / ell_k: dK / d log ell_k = -2 xs_ik xs_jk, so the tile's share of
+// hyper k is -2 sum_e w_e xs_rk xs_ck over the thread's 16 entries (w: Hadamard weight, 0 outside the upper triangle and the
+// matrix), reduced over the block: all D length-scales in the one sweep.  The coordinates come from global memory (the tile's two
+// 512-byte runs per coordinate, cached); D block sums per tile.
+__device__ __forceinline__ void lin_dim_reduce(const double* __restrict__ XT, long ldp, long r0, long c0, const double (&w)[4][4],
+                                               int D, double* red, double* __restrict__ out) {
+    const int t = threadIdx.x, tr = t >> 4, tc = t & 15;
+#pragma unroll 1
+    for (int k = 0; k < D; ++k) {
+        const double* xk = XT + (long)k * ldp;
+        const double2_t r01 = *(const double2_t*)(xk + r0 + 4 * tr);
+        const double2_t r23 = *(const double2_t*)(xk + r0 + 4 * tr + 2);
+        const double2_t c01 = *(const double2_t*)(xk + c0 + 2 * tc);
+        const double2_t c23 = *(const double2_t*)(xk + c0 + 2 * tc + 32);
+        const double rv[4] = {r01[0], r01[1], r23[0], r23[1]};
+        const double cv[4] = {c01[0], c01[1], c23[0], c23[1]};
+        double acc = 0.0;
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) acc = fma(w[a][b] * rv[a], cv[b], acc);
+        const double tot = block_sum(acc, red);
+        if (t == 0) out[k] = -2.0 * tot;
+    }
+}
+
 // Same reduction for a composite program: per element the leaf values, their (up to three) derivatives and the
 // chain-rule weights through the Sum/Product/Scale tree.  Elements run in a rolled loop over LDS-staged distances
 // so that the leaf functors are instantiated once.
@@ -565,7 +591,11 @@ __global__ __launch_bounds__(256) void point_norm_kernel(const double* __restric
 // per leaf).  The second leaf's distance and weights stay in registers (sel16 / put16): static LDS ends at 64 KB.
 // PRE: the program has a precomputed-matrix leaf (cov.Pre): its tile of the resident M2 is loaded with 16-byte loads beside the
 // distances; it has no hypers of its own but weights every other leaf's derivative and carries the Scale nodes above it.
-template <int NARD, bool PRE = false>
+// DOT: the program has dot-product leaves (P.dot_mask: cov.Linear / cov.Poly, or plain cov.LINard as a one-leaf program on scaled
+// coordinates): p = sum_k x_k z_k is accumulated beside the distances in the same pass over the coordinates (dot_tile) and stays in
+// registers.  NARD <= 1 then (the dot product is the second extra accumulator), and no PRE.  A LINard leaf has one hyper per
+// coordinate: g_k = sum_ij wq_ij (-2 xs_ik xs_jk) in a second pass over the coordinates (lin_dim_reduce).
+template <int NARD, bool PRE = false, bool DOT = false>
 __global__ __launch_bounds__(256) void hadamard_prog_kernel(const double* __restrict__ XT, long ldp, long n, int dpad,
                                                             CovProgram P, int ncov, double inv_sn2, double sn2,
                                                             const double* __restrict__ Binv, long ldb,
@@ -584,7 +614,9 @@ __global__ __launch_bounds__(256) void hadamard_prog_kernel(const double* __rest
     const long ti = r, tj = ti + (b - (r * nt - r * (r - 1) / 2));
     const long r0 = ti * ST, c0 = tj * ST;
     double s[4][4], s1[PARD ? 4 : 1][4], s2[PARD2 ? 4 : 1][4], w2[PARD2 ? 4 : 1][4];
-    if constexpr (PARD2) sqdist_tile3(XT, ldp, r0, XT, ldp, c0, dpad, P.ardw, P.ardw2, sm, s, s1, s2);
+    double pdt[DOT ? 4 : 1][4];
+    if constexpr (DOT) dot_tile<PARD>(XT, ldp, r0, XT, ldp, c0, dpad, P.ardw, sm, s, s1, pdt);
+    else if constexpr (PARD2) sqdist_tile3(XT, ldp, r0, XT, ldp, c0, dpad, P.ardw, P.ardw2, sm, s, s1, s2);
     else if constexpr (PARD) sqdist_tile2(XT, ldp, r0, XT, ldp, c0, dpad, P.ardw, sm, s, s1);
     else sqdist_tile(XT, ldp, r0, XT, ldp, c0, dpad, sm, s);
     if constexpr (PARD2) {
@@ -613,7 +645,7 @@ __global__ __launch_bounds__(256) void hadamard_prog_kernel(const double* __rest
         const long cc = c0 + 2 * tc + (bq & 1) + 32 * (bq >> 1);
         double wt = (cc > rr) ? 2.0 : (cc == rr ? 1.0 : 0.0);
         if (rr >= n || cc >= n) wt = 0.0;
-        if (wt == 0.0) { if (PARD) sv1[e * 256] = 0.0; continue; }
+        if (wt == 0.0) { if (PARD) sv1[e * 256] = 0.0; if constexpr (DOT) put16(pdt, e, 0.0); continue; }
         const double wr = wv ? wv[rr] : inv_sn2, wc = wv ? wv[cc] : 1.0;
         const double q = Binv[rr * ldb + cc] * (wr * wc) - alpha[rr] * alpha[cc];
         const double wq = wt * q;
@@ -624,13 +656,19 @@ __global__ __launch_bounds__(256) void hadamard_prog_kernel(const double* __rest
         double ardfac = 0.0, ardfac2 = 0.0;   // dK_l / d log ell_k = ardfac * (scaled squared difference in coordinate k)
         double pve = 0.0;
         if constexpr (PRE) pve = sel16(pm, e);
+        double pde = 0.0, linw = 0.0;         // DOT: the element's dot product; the weight wq dK/dk_l of a LINard leaf
+        if constexpr (DOT) pde = sel16(pdt, e);
 #pragma unroll
         for (int l = 0; l < CP_MAXLEAF; ++l) {
             v[l] = 1.0; d[l][0] = d[l][1] = d[l][2] = 0.0;
             if (l < P.nleaf) {
                 const bool a1 = PARD && l == P.ard_leaf, a2 = PARD2 && l == P.ard_leaf2;
+                bool dl = false;
+                if constexpr (DOT) dl = (P.dot_mask >> l) & 1u;
                 if (PRE && l == P.pre_leaf) {
                     v[l] = pve;                       // no hypers: d[l][.] stay zero
+                } else if (DOT && dl) {
+                    dot_value_deriv_all(P.leaf[l], pde, same, v[l], d[l][0], d[l][1]);
                 } else if (a1 || a2) {
                     // d[l][0]: magnitude hyper, d[l][1]: RQard shape hyper (Core/cov.py:922-936, 1412-1425)
                     double sl = sv1[e * 256];
@@ -667,8 +705,10 @@ __global__ __launch_bounds__(256) void hadamard_prog_kernel(const double* __rest
                 gl[l][2] = fma(wl, d[l][2], gl[l][2]);
                 if (PARD && l == P.ard_leaf) sv1[e * 256] = wl * ardfac;
                 if constexpr (PARD2) { if (l == P.ard_leaf2) put16(w2, e, wl * ardfac2); }
+                if constexpr (DOT) { if (P.leaf[l].kind == 15) linw = wl; }
             }
         }
+        if constexpr (DOT) put16(pdt, e, linw);       // the dot product is consumed: its slot carries the LINard weight out
 #pragma unroll
         for (int k = 0; k < CP_MAXSCALE; ++k) {
             if (k < P.nscale) {
@@ -684,6 +724,7 @@ __global__ __launch_bounds__(256) void hadamard_prog_kernel(const double* __rest
 #pragma unroll
     for (int l = 0; l < CP_MAXLEAF; ++l) {
         if (l < P.nleaf) {
+            if constexpr (DOT) { if (P.leaf[l].kind == 15) continue; }           // LINard: D length-scales and nothing else (below)
             if ((PARD && l == P.ard_leaf) || (PARD2 && l == P.ard_leaf2)) {      // ARD leaf: D length-scales (below), magnitude, [shape]
                 const int D = P.leaf[l].D;
                 const double t0 = block_sum(gl[l][0], red);
@@ -715,6 +756,10 @@ __global__ __launch_bounds__(256) void hadamard_prog_kernel(const double* __rest
             if (mu) ard_dim_reduce(XT, ldp, r0, c0, dpad, sm, w2, P.ardw2, mu, P.leaf[lb].D, out + P.hyp0[lb]);
             else ard_dim_reduce_diff(XT, ldp, r0, c0, dpad, sm, w2, P.ardw2, P.leaf[lb].D, out + P.hyp0[lb]);
         }
+    }
+    if constexpr (DOT) {
+        for (int l = 0; l < P.nleaf; ++l)
+            if (P.leaf[l].kind == 15) { __syncthreads(); lin_dim_reduce(XT, ldp, r0, c0, pdt, P.leaf[l].D, red, out + P.hyp0[l]); }
     }
 #pragma unroll
     for (int k = 0; k < CP_MAXSCALE; ++k) {
@@ -1111,6 +1156,14 @@ int hadamard_partial_launch(const double* XT, long ldp, long n, long np, int dpa
                                            ncov, 1.0 / sn2, sn2, Binv, ldb, alpha, wv, partial, nt, mu, b0)
             if (pg.ard_leaf2 >= 0) PRE_HLAUNCH(2); else if (pg.ard_leaf >= 0) PRE_HLAUNCH(1); else PRE_HLAUNCH(0);
 #undef PRE_HLAUNCH
+        } else if (pg.dot_mask) {
+            if (pg.ard_leaf2 >= 0) return -13;        // the dot product is the second extra accumulator
+            if (pg.ard_leaf >= 0)
+                hipLaunchKernelGGL((hadamard_prog_kernel<1, false, true>), dim3((unsigned)nblk), dim3(256), 0, st, XT, ldp, n, dpad, pg,
+                                   ncov, 1.0 / sn2, sn2, Binv, ldb, alpha, wv, partial, nt, mu, b0);
+            else
+                hipLaunchKernelGGL((hadamard_prog_kernel<0, false, true>), dim3((unsigned)nblk), dim3(256), 0, st, XT, ldp, n, dpad, pg,
+                                   ncov, 1.0 / sn2, sn2, Binv, ldb, alpha, wv, partial, nt, mu, b0);
         } else if (pg.ard_leaf2 >= 0)
             hipLaunchKernelGGL(hadamard_prog_kernel<2>, dim3((unsigned)nblk), dim3(256), 0, st, XT, ldp, n, dpad, pg, ncov,
                                1.0 / sn2, sn2, Binv, ldb, alpha, wv, partial, nt, mu, b0);

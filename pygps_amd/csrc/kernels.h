@@ -33,6 +33,8 @@ int cov_factor_panel_launch(const double* XT, long ldp, long n, long np, int dpa
 int cov_self_launch(const CovSpec& cs, int train, double* out_dev, hipStream_t st);
 int cov_self_vec_launch(const CovSpec& cs, int train, const double* pre, long stride, long m, double* out_dev, int sub,
                         hipStream_t st);
+int cov_self_dot_launch(const CovSpec& cs, int train, const double* XT, long ld, int dpad, long m, double* out_dev, int sub,
+                        hipStream_t st);
 int self_fill_launch(double* out, long m, double val, hipStream_t st);
 
 // grad.hip

@@ -296,7 +296,7 @@ static int laplace_fit_core(pgp_ctx* c, const double* Kdense, int kind, const do
     else { const int rc = make_spec(c, kind, covhyp, ncov, para, flags, -1, d, cp); if (rc != PGP_OK) return rc == -11 ? -10 : rc; }
     CHK(ensure_workspace(c, np));
     double kss = 0.0;
-    if (!dense) CHK(cov_point_value(c, cp, 2, &kss));
+    if (!dense && !cp.has_dot()) CHK(cov_point_value(c, cp, 2, &kss));          // only stored for predict (dot-product leaves: per point there)
     const long need = std::max<long>(hadamard_partial_count(np, ncov), np);
     if (want >= 3 && c->partial_cap < need) {
         if (c->partial) (void)hipFree(c->partial);

@@ -234,7 +234,9 @@ int pgp_predict(pgp_ctx* c, pgp_factor* f, const double* xs, int64_t ns, const d
     // points, ns test points.  It is stored test-major, the orientation of the blocked solve's cross block, so that form serves
     const bool pre = f->cs.has_pre();
     if (pre && (!c->pre1t || !c->pre1s || c->pre_n != n || c->pre_ns != ns || c->pre_ld != np)) return -15;
-    const bool product = !pre && np >= 1024 && (c->predict_inverse == 2 || (c->predict_inverse == 1 && (f->Linv != nullptr || f->Eraw != nullptr || ns >= 1024)));
+    // dot-product leaves: k(z,z) differs per test point too -- the blocked solve with the vector taken from the batch's coordinates
+    const bool dotk = f->cs.has_dot();
+    const bool product = !pre && !dotk && np >= 1024 && (c->predict_inverse == 2 || (c->predict_inverse == 1 && (f->Linv != nullptr || f->Eraw != nullptr || ns >= 1024)));
     if (product) CHK(ensure_linv(c, f));
     else CHK(ensure_wd(c, f));
     // test points per batch (the reference uses 1000): up to predict_batch = 65536 within 16 GiB of scratch, so that the K = 128
@@ -298,6 +300,9 @@ int pgp_predict(pgp_ctx* c, pgp_factor* f, const double* xs, int64_t ns, const d
         if (pre) {                               // k(z,z) differs per test point: raw sums of squares, then max(k_jj - s_j, 0)
             CHK(col_sumsq_launch(Ks, np, n, nb_, 0.0, -(f->sWv ? 1.0 : f->sw * f->sw), o2, st));
             CHK(cov_self_vec_launch(cp, 2, c->pre1s + a, 1, nb_, o2, 1, st));
+        } else if (dotk) {
+            CHK(col_sumsq_launch(Ks, np, n, nb_, 0.0, -(f->sWv ? 1.0 : f->sw * f->sw), o2, st));
+            CHK(cov_self_dot_launch(cp, 2, XcT, ldc, dpad, nb_, o2, 1, st));
         } else
         CHK(col_sumsq_launch(Ks, np, n, nb_, f->kss, f->sWv ? 1.0 : f->sw * f->sw, o2, st));
         }

@@ -56,6 +56,10 @@ struct CovProgram {
     int pre_leaf;
     const double* pre;
     long pre_ld;
+    // dot-product leaves (cov.Linear, cov.Poly; plain cov.LINard as a one-leaf program on coordinates scaled by 1 / ell_k): bit l =
+    // leaf l.  Their argument is p = sum_k x_k z_k, accumulated beside r^2 by the DOT instantiations of the tile kernels and by no
+    // other; 0 for every other program.  One accumulator serves all of them.
+    unsigned dot_mask;
 };
 
 // Spectral mixture kernel (Wilson & Adams 2013; Core/cov.py:454-619, GPML covSM with the product over the coordinates):
@@ -199,6 +203,57 @@ __device__ __forceinline__ void sqdist_tile3(const double* __restrict__ XrT, lon
                     s[a][b] += d2;
                     s1[a][b] = fma(wk, d2, s1[a][b]);
                     s2[a][b] = fma(wk2, d2, s2[a][b]);
+                }
+        }
+        __syncthreads();
+    }
+}
+
+// the tile of a program with dot-product leaves: p = sum_k a_k b_k by fma in coordinate order beside r^2 (and beside the ARD leaf's
+// weighted distance when ARD), one read of the coordinates.  The distances are accumulated exactly as sqdist_tile / sqdist_tile2 do.
+template <bool ARD>
+__device__ __forceinline__ void dot_tile(const double* __restrict__ XrT, long ldr, long r0,
+                                         const double* __restrict__ XcT, long ldc, long c0, int dpad,
+                                         const double* __restrict__ w /* ARD: uniform, >= min(dpad, CP_MAXARD) entries */,
+                                         double* __restrict__ sm, double (&s)[4][4], double (&s1)[ARD ? 4 : 1][4],
+                                         double (&pd)[4][4]) {
+    const int t = threadIdx.x, tr = t >> 4, tc = t & 15;
+    double* xr = sm;
+    double* xc = sm + SKC * ST;
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) { s[a][b] = 0.0; pd[a][b] = 0.0; if (ARD) s1[a][b] = 0.0; }
+    for (int k0 = 0; k0 < dpad; k0 += SKC) {
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const int v = t + p * 256;
+            const int k = v >> 5, pr = v & 31;
+            *(double2_t*)(xr + k * ST + 2 * pr) = *(const double2_t*)(XrT + (long)(k0 + k) * ldr + r0 + 2 * pr);
+            *(double2_t*)(xc + k * ST + 2 * pr) = *(const double2_t*)(XcT + (long)(k0 + k) * ldc + c0 + 2 * pr);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < SKC; ++k) {
+            double wk = 0.0;
+            if (ARD) wk = (k0 + k) < CP_MAXARD ? w[k0 + k] : 0.0;
+            const double2_t r01 = *(const double2_t*)(xr + k * ST + 4 * tr);
+            const double2_t r23 = *(const double2_t*)(xr + k * ST + 4 * tr + 2);
+            const double2_t c01 = *(const double2_t*)(xc + k * ST + 2 * tc);
+            const double2_t c23 = *(const double2_t*)(xc + k * ST + 2 * tc + 32);
+            const double rv[4] = {r01[0], r01[1], r23[0], r23[1]};
+            const double cv[4] = {c01[0], c01[1], c23[0], c23[1]};
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    const double df = rv[a] - cv[b];
+                    if (ARD) {
+                        const double d2 = df * df;
+                        s[a][b] += d2;
+                        s1[a][b] = fma(wk, d2, s1[a][b]);
+                    } else s[a][b] = fma(df, df, s[a][b]);
+                    pd[a][b] = fma(rv[a], cv[b], pd[a][b]);
                 }
         }
         __syncthreads();
@@ -432,6 +487,42 @@ __device__ __forceinline__ double cov_deriv(const CovParams& p, double s, double
                       : 2.0 * p.sf2 * matern_poly(p.md, t) *  exp_nonpos(-t);
 }
 
+// ---- dot-product kernels (Core/cov.py:623-679, 986-1074): maps of p = sum_k x_k z_k, not of a distance.  Kept out of cov_value /
+// cov_deriv: only the DOT instantiations of the program evaluator call them.  J = 1e-10 on the training diagonal (:649, :1003, :1050).
+//   Linear (13): sf2 (p + J), sf2 = exp(hyp0);  der 0: 2 sf2 p.
+//   Poly (14):   sf2 (c + p + J)^d, c = alpha, d = md, sf2 = exp(2 hyp1);  der 0: c d sf2 (c + p)^(d-1), der 1: 2 sf2 (c + p)^d, der 2: 0.
+//   LINard (15): p + J on coordinates scaled by 1 / ell_k (sf2 = 1);  der k: -2 dk, dk = the product of the scaled k-th coordinates.
+__device__ __forceinline__ bool cov_is_dot(const CovParams& p) { return p.kind >= 13 && p.kind <= 15; }
+__device__ __forceinline__ double dot_value(const CovParams& p, double pd, bool same) {
+    const double a = pd + ((p.train == 1 && same) ? 1e-10 : 0.0);
+    if (p.kind == 14) return p.sf2 * ipow(p.alpha + a, p.md);
+    return p.sf2 * a;
+}
+__device__ __forceinline__ double dot_deriv(const CovParams& p, double pd, double dk) {
+    if (p.kind == 14) {
+        const double b = p.alpha + pd;
+        if (p.der == 0) return p.alpha * (double)p.md * p.sf2 * ipow(b, p.md - 1);
+        return p.der == 1 ? 2.0 * p.sf2 * ipow(b, p.md) : 0.0;
+    }
+    if (p.kind == 15) return -2.0 * dk;
+    return 2.0 * p.sf2 * pd;
+}
+// value and the (up to two) derivatives of Linear / Poly in one go: the gradient pass
+__device__ __forceinline__ void dot_value_deriv_all(const CovParams& p, double pd, bool same, double& v, double& d0, double& d1) {
+    const double a = pd + ((p.train == 1 && same) ? 1e-10 : 0.0);
+    d1 = 0.0;
+    if (p.kind == 14) {
+        const double b = p.alpha + pd;
+        const double b1 = ipow(b, p.md - 1);
+        v = p.sf2 * ipow(p.alpha + a, p.md);
+        d0 = p.alpha * (double)p.md * p.sf2 * b1;
+        d1 = 2.0 * p.sf2 * (b1 * b);
+        return;
+    }
+    v = p.sf2 * a;
+    d0 = p.kind == 15 ? 0.0 : 2.0 * p.sf2 * pd;      // LINard: per-coordinate sums, taken by the caller
+}
+
 // every derivative (up to three hypers) of the non-ARD kernels, transcendental functions evaluated once
 template <bool EXT = false>
 __device__ __forceinline__ void cov_deriv_all(const CovParams& p, double s, double& d0, double& d1, double& d2,
@@ -558,7 +649,11 @@ struct CovSpec {
     const double* pre_train = nullptr;   // M2, zero-padded to pre_rows x pre_ld
     const double* pre_cross = nullptr;   // rows = test points of the current predict batch, columns = training points (same pre_ld)
     long pre_ld = 0, pre_rows = 0, pre_cross_rows = 0;
-    bool has_pre() const { return prog && pg.pre_leaf >= 0; }      // a cov.Pre leaf: the diagonal and k(z,z) differ from point to point
+    bool has_pre() const { return prog && pg.pre_leaf >= 0; }      // a cov.Pre leaf: its values are read from the bound matrices
+    bool has_dot() const { return prog && pg.dot_mask != 0u; }     // dot-product leaves (Linear, Poly, plain LINard)
+    // the diagonal and k(z,z) differ from point to point: no scalar K_ii / k(z,z) exists (cov_point_value), 'self_test' is a
+    // per-point vector, pgp_predict takes the blocked solve with a k(z,z) vector, EP reads K_ii off the assembled matrix
+    bool diag_per_point() const { return has_pre() || has_dot(); }
 };
 
 // the spectral mixture description of a spec with its derivative index (cp.der, hyp layout of CovSM::h) resolved
@@ -627,15 +722,21 @@ __device__ __forceinline__ void pre_tile_load(const double* __restrict__ pre, lo
 }
 
 // pv: the element's value of the precomputed-matrix leaf (P.pre_leaf), loaded by the caller
-__device__ __forceinline__ double prog_leaf_value(const CovProgram& P, int l, double r2, bool same, double s1, double s2, double pv) {
+// DOT (here and below): the program has dot-product leaves (P.dot_mask), pd is the element's dot product.  DOT = false compiles to
+// what these functions were before the dot-product leaves existed.
+template <bool DOT = false>
+__device__ __forceinline__ double prog_leaf_value(const CovProgram& P, int l, double r2, bool same, double s1, double s2, double pv,
+                                                  double pd = 0.0) {
+    if constexpr (DOT) { if ((P.dot_mask >> l) & 1u) return dot_value(P.leaf[l], pd, same); }
     return l == P.pre_leaf ? pv : cov_value<true>(P.leaf[l], prog_leaf_dist(P, l, r2, s1, s2), same);
 }
 
+template <bool DOT = false>
 __device__ __forceinline__ double prog_value(const CovProgram& P, double r2, bool same, double s1 = 0.0, double s2 = 0.0,
-                                             double pv = 0.0) {
+                                             double pv = 0.0, double pd = 0.0) {
     double v[CP_MAXLEAF], T[CP_MAXTERM];
 #pragma unroll
-    for (int l = 0; l < CP_MAXLEAF; ++l) v[l] = l < P.nleaf ? prog_leaf_value(P, l, r2, same, s1, s2, pv) : 1.0;
+    for (int l = 0; l < CP_MAXLEAF; ++l) v[l] = l < P.nleaf ? prog_leaf_value<DOT>(P, l, r2, same, s1, s2, pv, pd) : 1.0;
     prog_terms(P, v, T);
     double K = 0.0;
 #pragma unroll
@@ -645,11 +746,13 @@ __device__ __forceinline__ double prog_value(const CovProgram& P, double r2, boo
 
 // derivative matrix entry for the flat hyper index P.der (Product :246-256, Sum :281-291, Scale :320-328)
 // dk2: ARD-weighted squared difference in coordinate der_j (only when the derivative is w.r.t. an ARD length-scale)
+// (a plain LINard leaf: dk2 is the product of the scaled coordinates der_j)
+template <bool DOT = false>
 __device__ __forceinline__ double prog_deriv(const CovProgram& P, double r2, bool same, double s1 = 0.0, double dk2 = 0.0,
-                                             double s2 = 0.0, double pv = 0.0) {
+                                             double s2 = 0.0, double pv = 0.0, double pd = 0.0) {
     double v[CP_MAXLEAF], T[CP_MAXTERM];
 #pragma unroll
-    for (int l = 0; l < CP_MAXLEAF; ++l) v[l] = l < P.nleaf ? prog_leaf_value(P, l, r2, same, s1, s2, pv) : 1.0;
+    for (int l = 0; l < CP_MAXLEAF; ++l) v[l] = l < P.nleaf ? prog_leaf_value<DOT>(P, l, r2, same, s1, s2, pv, pd) : 1.0;
     if (P.der_scale >= 0) {               // 2 * exp(h) * child, through whatever sits above the Scale node
         prog_terms(P, v, T);
         double K = 0.0;
@@ -664,7 +767,10 @@ __device__ __forceinline__ double prog_deriv(const CovProgram& P, double r2, boo
         if (l == P.der_leaf) {
             CovParams lp = P.leaf[l];
             lp.der = P.der_j;
-            out = prog_leaf_weight(P, v, l) * cov_deriv<true>(lp, prog_leaf_dist(P, l, r2, s1, s2), dk2, same);
+            bool dot = false;
+            if constexpr (DOT) dot = (P.dot_mask >> l) & 1u;
+            if (DOT && dot) out = prog_leaf_weight(P, v, l) * dot_deriv(lp, pd, dk2);
+            else out = prog_leaf_weight(P, v, l) * cov_deriv<true>(lp, prog_leaf_dist(P, l, r2, s1, s2), dk2, same);
         }
     }
     return out;
@@ -674,9 +780,14 @@ __device__ __forceinline__ double prog_deriv(const CovProgram& P, double r2, boo
 __device__ __forceinline__ double cov_elem(const CovParams& p, double s, double dk2, bool same) {
     return p.der < 0 ? cov_value(p, s, same) : cov_deriv(p, s, dk2, same);
 }
+template <bool DOT = false>
 __device__ __forceinline__ double cov_elem(const CovProgram& P, double s, double dk2, bool same, double s1 = 0.0,
-                                           double s2 = 0.0, double pv = 0.0) {
-    return P.der < 0 ? prog_value(P, s, same, s1, s2, pv) : prog_deriv(P, s, same, s1, dk2, s2, pv);
+                                           double s2 = 0.0, double pv = 0.0, double pd = 0.0) {
+    return P.der < 0 ? prog_value<DOT>(P, s, same, s1, s2, pv, pd) : prog_deriv<DOT>(P, s, same, s1, dk2, s2, pv, pd);
+}
+// plain LINard: the coordinate whose product the derivative needs (-1: none)
+__device__ __forceinline__ int cov_dot_der(const CovProgram& P) {
+    return (P.der >= 0 && P.der_leaf >= 0 && P.leaf[P.der_leaf & 7].kind == 15) ? P.der_j : -1;
 }
 __device__ __forceinline__ int cov_ard_der(const CovParams& p) { return (cov_is_ard(p) && p.der >= 0 && p.der < p.D) ? p.der : -1; }
 __device__ __forceinline__ int cov_ard_der(const CovProgram& P) {

@@ -470,6 +470,8 @@ class GPMC(object):
         if not self.shared_kernel:
             return "pairs"
         m, k = self._prior()
+        if isinstance(k, cov.Kernel) and k._dot_leaves():
+            return "pairs"                                # the shared engine predicts with one scalar k(z, z)
         if isinstance(k, cov._Composite):
             if not k._on_device():
                 return "pairs"

@@ -336,6 +336,7 @@ class Exact(Inference):
             raise Exception("Exact inference only possible with Gaussian likelihood")
         if self.sharded:
             _cov.refuse_pre(covfunc, "a sharded fit (the panels of a distributed factor are assembled per rank)")
+            _cov.refuse_dot(covfunc, "a sharded fit")
         _check_pre(covfunc, x)
         if _dense_route(covfunc):
             if self.sharded:
@@ -620,6 +621,7 @@ class FITC_Exact(Inference):
         if not isinstance(covfunc, _cov.FITCOfKernel):
             raise Exception('Only covFITC supported.')
         _cov.refuse_pre(covfunc.covfunc, "the FITC approximation (fitc(u) of a precomputed matrix has no meaning)")
+        _cov.refuse_dot(covfunc.covfunc, "the FITC approximation")
         dev = _lib.default_device() if self.device is None else self.device
         kind, para, flags = _device_kernel(covfunc.covfunc, _lib.ctx(dev))
         x = _lib.f64(x)
@@ -687,6 +689,7 @@ class FITC_EP(Inference):
         if not isinstance(covfunc, _cov.FITCOfKernel):
             raise NotImplementedError("pygps_amd: FITC_EP needs a FITC covariance (covfunc.fitc(u)); only covFITC is supported")
         _cov.refuse_pre(covfunc.covfunc, "the FITC approximation (fitc(u) of a precomputed matrix has no meaning)")
+        _cov.refuse_dot(covfunc.covfunc, "the FITC approximation")
         if isinstance(likfunc, _lik.Laplace):
             lik, likhyp = _lib.LIK_LAPLACE, _lib.f64(np.asarray(likfunc.hyp, dtype=float).reshape(-1))
         elif isinstance(likfunc, _lik.Erf):
