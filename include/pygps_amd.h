@@ -185,6 +185,44 @@ void pgp_factor_free(pgp_ctx* ctx, pgp_factor* f);
 int pgp_predict(pgp_ctx* ctx, pgp_factor* f, const double* xs, int64_t ns, const double* ms, double* fmu,
                 double* fs2);
 
+/* ---- the joint posterior at the test points and draws from it (csrc/joint.hip; no reference counterpart: Core/gp.py:395-417
+ * stops at the marginals).  With V = R'^-1 (sW o Ks):
+ *      fmu  = ms + Ks' alpha                          as pgp_predict
+ *      fcov = Kss - V'V                               Kss = k(xs, xs) in 'train' mode (cov.Noise: sf2 I); its diagonal is the
+ *                                                     'self_test' one: diag(fcov) is pgp_predict's fs2, clipped at 0 like it
+ *      A    = fcov + (noise + jitter) I = Lc Lc'      the matrix that is factorised
+ *      F    = fmu 1' + Lc Z                           Z (ns, nsamp) row-major: standard normal draws, made by the caller
+ * All ns <= PGP_JOINT_MAX_POINTS points are one batch; V takes the form (product or blocked solve) pgp_predict would take for
+ * them.  Outputs, row-major: fmu (ns); cov_out (ns, ns), exactly symmetric (one triangle computed, then mirrored), or NULL;
+ * chol_out (ns, ns), the lower factor Lc with exact zeros above the diagonal, or NULL; samples_out (ns, nsamp) or NULL (then Z
+ * and nsamp are ignored).  The factorisation runs only when chol_out or samples_out is given.  stage_ms_out (5, optional):
+ * device ms of cross block + V | Kss | V'V | factorisation | draws and the downloads of cov_out / chol_out / samples_out, from
+ * the call's own events (pgp_last_timings is not touched).  The posterior handle keeps nothing beyond what pgp_predict may
+ * leave on it.
+ * The factor is the Cholesky sweep's after one Newton step L <- L + L Phi(Y), Y = L^-1 (A - L L') L^-T, which brings its
+ * componentwise residual to a substitution-based Cholesky's on badly conditioned A.  The step is first order in Y and is taken
+ * only where nsp^2 max|Y| <= 1 (nsp = ns rounded up to 128): on a barely positive definite A that the sweep got through with
+ * pivots at rounding level Y is not small, and the sweep's own factor is returned as it is, with status 0.  Option
+ * "joint_refine" 0 always returns the sweep's factor, at an eighth of the factorisation time.
+ * Kss is assembled in the difference form at every size, like the cross block it is subtracted from; the Gram-form assembly of
+ * the fits is gated by a bound on the resident TRAINING inputs (gram_assembly_applies), which says nothing about xs.
+ * Status: > 0 the first non-positive pivot of A (1-based, at most ns); -4 ns < 1 or ns > PGP_JOINT_MAX_POINTS (nothing is
+ * allocated); -8 samples_out with nsamp < 1 or without Z; -13 a program with a PGP_COV_PRE leaf (cov.Pre carries no k(xs, xs));
+ * otherwise as pgp_predict.
+ * pgp_predict_joint_dense: the same for posteriors of caller-built matrices (pgp_exact_fit_dense ...): Ks (n, ns) =
+ * getCovMatrix(x, xs, 'cross'), Kss (ns, ns) = getCovMatrix(xs, 'train') with the 'self_test' values on its diagonal.
+ * pgp_sample_mvn: factor and draws for a caller's symmetric matrix A (ns, ns) and mean (ns, or NULL): A + jitter I = Lc Lc',
+ * F = mean 1' + Lc Z (GP.sample_prior). */
+#define PGP_JOINT_MAX_POINTS 16384
+int pgp_predict_joint(pgp_ctx* ctx, pgp_factor* f, const double* xs, int64_t ns, const double* ms, double noise, double jitter,
+                      const double* Z, int64_t nsamp, double* fmu, double* cov_out, double* chol_out, double* samples_out,
+                      double* stage_ms_out);
+int pgp_predict_joint_dense(pgp_ctx* ctx, pgp_factor* f, const double* Ks, const double* Kss, int64_t ns, const double* ms,
+                            double noise, double jitter, const double* Z, int64_t nsamp, double* fmu, double* cov_out,
+                            double* chol_out, double* samples_out, double* stage_ms_out);
+int pgp_sample_mvn(pgp_ctx* ctx, const double* A, int64_t ns, const double* mean, double jitter, const double* Z, int64_t nsamp,
+                   double* chol_out, double* samples_out);
+
 /* ---- the same path from CALLER-BUILT covariance matrices (csrc/dense.hip) ---------------------------------
  * For covariance functions that are not device programs (Core/cov.py:230-328 composes anything; a tree with more than two
  * ARD leaves or more than 8 leaves has getCovMatrix / getDerMatrix only): K (n,n) = getCovMatrix(x, 'train'), r = y - m.

@@ -31,6 +31,8 @@ PROP_NONE, PROP_T, PROP_SPREAD = 0, 1, 2
 PROP_MAX_LABELS = 256             # label classes of pgp_propagation_kernel (include/pygps_amd.h)
 PROP_SORT_LDS = 2048              # keys of one graph sorted on chip; PROP_GRAM_LDS (key, count) pairs of a tile of 32 graphs held on chip
 PROP_GRAM_LDS = 5120
+JOINT_MAX_POINTS = 16384          # test points of pgp_predict_joint / pgp_sample_mvn (include/pygps_amd.h)
+JOINT_STAGES = ("cross_v", "kss", "vtv", "potrf", "draws")
 PROP_STAGES = ("upload", "update", "hash", "sort", "gram", "download")
 FLAG_MATERN_REFERENCE_DER = 1
 STAGES = ("assemble", "potrf", "solve", "trtri", "lauum", "grad", "total")
@@ -63,6 +65,10 @@ SIGNATURES = {
     "pgp_factor_n": (_i64, [_vp]),
     "pgp_factor_free": (None, [_vp, _vp]),
     "pgp_predict": (C.c_int, [_vp, _vp, _dp, _i64, _dp, _dp, _dp]),
+    "pgp_predict_joint": (C.c_int, [_vp, _vp, _dp, _i64, _dp, C.c_double, C.c_double, _dp, _i64, _dp, _dp, _dp, _dp, _dp]),
+    "pgp_predict_joint_dense": (C.c_int, [_vp, _vp, _dp, _dp, _i64, _dp, C.c_double, C.c_double, _dp, _i64, _dp, _dp, _dp, _dp,
+                                          _dp]),
+    "pgp_sample_mvn": (C.c_int, [_vp, _dp, _i64, _dp, C.c_double, _dp, _i64, _dp, _dp]),
     "pgp_exact_fit_dense": (C.c_int, [_vp, _dp, _i64, _dp, C.c_double, C.c_int, _dp, _dp, _dp, C.POINTER(_vp)]),
     "pgp_dense_grad_term": (C.c_int, [_vp, _dp, _i64, C.c_double, _dp]),
     "pgp_predict_dense": (C.c_int, [_vp, _vp, _dp, _i64, _dp, _dp, _dp, _dp]),
@@ -146,6 +152,8 @@ TEST_SIGNATURES = {
     "pgp_test_gather_sym": (C.c_int, [_vp, _dp, _i64, C.POINTER(C.c_int32), _i64, _i64, _dp, _dp, _dp, _dp]),
     "pgp_test_vote": (C.c_int, [_vp, _dp, _dp, _i64, C.c_int, C.c_int, C.c_int, _dp, _dp]),
     "pgp_test_yield_table": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
+    "pgp_test_joint_vpad": (C.c_int, [_vp, _vp, _dp, _i64, C.POINTER(C.c_int), C.POINTER(_i64)]),
+    "pgp_test_pool_state": (C.c_int, [_vp, _vp, C.POINTER(_i64)]),
 }
 
 _lock = threading.RLock()

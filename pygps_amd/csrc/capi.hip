@@ -188,6 +188,7 @@ int pgp_device_info(pgp_ctx* c, int* n_cu, int* sclk_mhz, double* hbm_gib, char*
 int pgp_set_option(pgp_ctx* c, const char* name, int value) {
     if (!c || !name) return -1;
     if (!strcmp(name, "nb_outer")) { if (value < 0) return -3; c->nb_outer = value; return PGP_OK; }
+    if (!strcmp(name, "joint_refine")) { c->joint_refine = value != 0; return PGP_OK; }
     if (!strcmp(name, "small_tile_below")) { c->small_tile_below = value; return PGP_OK; }
     if (!strcmp(name, "trtri_small_tile_below")) { c->trtri_small_tile_below = value; return PGP_OK; }
     if (!strcmp(name, "xcd_order")) { c->xcd_order = value; return PGP_OK; }

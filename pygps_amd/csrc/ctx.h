@@ -1,6 +1,7 @@
 // Internal: context / factor structs shared by the host-side drivers (capi.hip, sweep.hip, predict.hip, ep.hip).
 #pragma once
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -121,6 +122,9 @@ struct pgp_ctx {
     size_t pool_bytes = 0;
     std::multimap<size_t, void*> spool; // general scratch (arbitrary contents)
     size_t spool_bytes = 0;
+    // scratch-pool buffers that are OUT: taken by a call (PoolScratch) or held by a posterior handle (spool_take) and not yet given
+    // back.  Accounting only (pgp_test_pool_state): a call that leaks a buffer leaves these above their value before it
+    std::atomic<long long> scratch_out_bytes{0}, scratch_out_count{0};
     // data
     long n = 0, d = 0, np = 0, ldf = 0;
     int dpad = 0;
@@ -166,6 +170,7 @@ struct pgp_ctx {
     int solve_outer = 8;                // leaves per outer panel of the blocked multi-rhs triangular solve (K = 128 solve_outer)
     int keep_inverse = 1;               // a fit with the fused inverse rows hands E = L^-T to its posterior handle (np <= 16384): predict's W without a trtri
     int predict_inverse = 1;            // pgp_predict: 0 = blocked solve, 1 = product form with W = L^-1 for batches >= 1024 points (or once W exists), 2 = always
+    int joint_refine = 1;               // pgp_predict_joint / pgp_sample_mvn: one Newton step on the factor behind the sweep (joint.hip joint_refine); 0 = the sweep's factor
     int predict_batch = 65536;          // test points per batch of pgp_predict (scratch: np x batch doubles, capped at 16 GiB -- predict_batch_points)
     int s_tile = 0;                     // tile size of the panel solves: 0 = automatic
     int gram_fast = 2, gram_grid = 32768; // Gram-form assembly: restructured kernel on / off, persistent workgroups (CovSpec)
@@ -270,16 +275,19 @@ static inline int spool_take(pgp_ctx* c, size_t bytes, void** out) {
             *out = it->second;
             c->spool.erase(it);
             c->spool_bytes -= bytes;
+            c->scratch_out_bytes += (long long)bytes; ++c->scratch_out_count;
             return PGP_OK;
         }
     }
     hipError_t e = pool_hip_malloc(out, bytes ? bytes : 8, "handle buffer");
     if (e != hipSuccess) { pgp_set_last_hip_error(e, "hipMalloc(handle buffer)", __FILE__, __LINE__); return PGP_ERR_HIP; }
+    c->scratch_out_bytes += (long long)bytes; ++c->scratch_out_count;
     return PGP_OK;
 }
 static inline void spool_give(pgp_ctx* c, size_t bytes, void* p) {
     if (!p) return;
     if (!c) { (void)hipFree(p); return; }
+    c->scratch_out_bytes -= (long long)bytes; --c->scratch_out_count;
     const size_t cap = pool_idle_cap(c);
     std::lock_guard<std::mutex> lk(c->pool_mu);
     if (c->spool_bytes + bytes > cap) { pool_hip_free(p, bytes, "scratch pool over its cap (handle buffer)"); return; }
@@ -334,6 +342,7 @@ struct PoolScratch {
         const size_t cap = pool_idle_cap(c);
         std::lock_guard<std::mutex> lk(c->pool_mu);
         for (auto& h : held) {
+            c->scratch_out_bytes -= (long long)h.first; --c->scratch_out_count;
             if (c->spool_bytes + h.first > cap) { pool_hip_free(h.second, h.first, "scratch pool over its cap"); continue; }
             c->spool.insert({h.first, h.second});
             c->spool_bytes += h.first;
@@ -355,6 +364,7 @@ struct PoolScratch {
             if (e != hipSuccess) { pgp_set_last_hip_error(e, "hipMalloc(pool scratch)", __FILE__, __LINE__); return PGP_ERR_HIP; }
         }
         held.push_back({bytes, p});
+        c->scratch_out_bytes += (long long)bytes; ++c->scratch_out_count;
         *out = (T*)p;
         return PGP_OK;
     }
@@ -466,6 +476,14 @@ int ensure_workspace(pgp_ctx* c, long np);
 int solve_lower_multi(pgp_ctx* c, const double* L, long ldl, const double* Wd, double* Y, long ldy, long np, int nrhs,
                       bool trans);
 int eet_lower(pgp_ctx* c, const double* E, long lde, double* Binv, long ldb, long np);
+// predict.hip, shared with joint.hip (pgp_predict_joint): the posterior handle's lazy operands, the pinned staging, the rule that
+// picks the form of V = L^-1 (sW o Ks), and one batch of the prediction in either form
+int ensure_wd(pgp_ctx* c, pgp_factor* f);
+int ensure_linv(pgp_ctx* c, pgp_factor* f);
+int pred_stage(pgp_ctx* c, size_t doubles);
+bool predict_takes_product(pgp_ctx* c, pgp_factor* f, long ns);
+int predict_batch(pgp_ctx* c, pgp_factor* f, const CovSpec& cp, bool product, long a, const double* XcT, long ldc, long nb, int nrhs,
+                  const double* msd, double* Ks, double* Vp, double* part, double* o1, double* o2, hipStream_t st);
 
 // ---- GPMC (gpmc.hip): one-vs-one pairs on one shared covariance matrix ----------------------------------------------------
 // The third source of the training covariance of the dense EP / Laplace drivers, beside "device program" and "dense upload":

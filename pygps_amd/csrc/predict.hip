@@ -61,7 +61,7 @@ int solve_lower_multi(pgp_ctx* c, const double* L, long ldl, const double* Wd /*
     return PGP_OK;
 }
 
-static int ensure_wd(pgp_ctx* c, pgp_factor* f) {
+int ensure_wd(pgp_ctx* c, pgp_factor* f) {
     if (f->Wd) return PGP_OK;
     CHK(spool_take(c, (size_t)128 * f->np * sizeof(double), (void**)&f->Wd));
     return leaf_inv_launch(f->F, f->ldf, f->Wd, 128, 128L * 128L, (int)(f->np / 128), c->st);
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(256) void kst_col_scale_kernel(double* __restrict__
 }
 }  // namespace
 
-static int ensure_linv(pgp_ctx* c, pgp_factor* f) {
+int ensure_linv(pgp_ctx* c, pgp_factor* f) {
     if (f->Linv) return PGP_OK;
     hipStream_t st = c->st;
     double* W = nullptr;
@@ -184,6 +184,46 @@ static int predict_batch_product(pgp_ctx* c, pgp_factor* f, const CovSpec& cp, c
     return col_sumsq_launch(V, np, n, nb_, f->kss, f->sWv ? 1.0 : f->sw * f->sw, o2, st);
 }
 
+// one batch through the blocked solve: Ks (np x nrhs column-major) receives the cross block and is overwritten by V
+static int predict_batch_solve(pgp_ctx* c, pgp_factor* f, const CovSpec& cp, long a, const double* XcT, long ldc, long nb_, int nrhs, const double* msd,
+                               double* Ks, double* o1, double* o2, hipStream_t st) {
+    const long np = f->np, n = f->n;
+    const int dpad = f->dpad;
+    const bool pre = f->cs.has_pre(), dotk = f->cs.has_dot();
+    // Ks as column-major (np x nrhs): rows = test points, columns = training points in the tile kernel's view
+    HIP_TRY(hipMemsetAsync(Ks, 0, (size_t)np * nrhs * sizeof(double), st));
+    CHK(cov_rect_launch(XcT, ldc, nb_, f->XsT, np, n, dpad, cp, Ks, np, st));
+    CHK(col_dot_full_launch(Ks, np, n, nb_, f->alpha, msd, o1, st));                  // fmu = ms + Ks' alpha
+    if (f->sWv) CHK(row_scale_launch(Ks, np, n, nrhs, f->sWv, st));                   // EP: sW o Ks
+    CHK(solve_lower_multi(c, f->F, f->ldf, f->Wd, Ks, np, np, nrhs, false));
+    if (pre) {                               // k(z,z) differs per test point: raw sums of squares, then max(k_jj - s_j, 0)
+        CHK(col_sumsq_launch(Ks, np, n, nb_, 0.0, -(f->sWv ? 1.0 : f->sw * f->sw), o2, st));
+        return cov_self_vec_launch(cp, 2, c->pre1s + a, 1, nb_, o2, 1, st);
+    }
+    if (dotk) {
+        CHK(col_sumsq_launch(Ks, np, n, nb_, 0.0, -(f->sWv ? 1.0 : f->sw * f->sw), o2, st));
+        return cov_self_dot_launch(cp, 2, XcT, ldc, dpad, nb_, o2, 1, st);
+    }
+    return col_sumsq_launch(Ks, np, n, nb_, f->kss, f->sWv ? 1.0 : f->sw * f->sw, o2, st);
+}
+
+// The form a call with ns test points takes: the product form (W = L^-1, one GEMM per batch) or the blocked solve.
+// A cov.Pre leaf stores its cross block test-major, the orientation of the blocked solve's cross block; dot-product leaves have a
+// k(z,z) per test point, taken from the batch's coordinates behind the blocked solve: both take that form.
+bool predict_takes_product(pgp_ctx* c, pgp_factor* f, long ns) {
+    return !f->cs.has_pre() && !f->cs.has_dot() && f->np >= 1024 &&
+           (c->predict_inverse == 2 || (c->predict_inverse == 1 && (f->Linv != nullptr || f->Eraw != nullptr || ns >= 1024)));
+}
+
+// One batch of pgp_predict, in either form (pgp_predict and pgp_predict_joint): the batch's nb_ points start at test point a, XcT
+// holds their scaled coordinates; o1 = fmu, o2 = fs2.  V = L^-1 (sW o Ks) is left np x nrhs column-major in Vp (product form; Ks
+// then holds the slabs of the transposed cross block) or in Ks (blocked solve), its padding rows and columns exact zeros.
+int predict_batch(pgp_ctx* c, pgp_factor* f, const CovSpec& cp, bool product, long a, const double* XcT, long ldc, long nb_, int nrhs,
+                  const double* msd, double* Ks, double* Vp, double* part, double* o1, double* o2, hipStream_t st) {
+    if (product) return predict_batch_product(c, f, cp, XcT, ldc, nb_, nrhs, msd, Ks, Vp, part, o1, o2, st);
+    return predict_batch_solve(c, f, cp, a, XcT, ldc, nb_, nrhs, msd, Ks, o1, o2, st);
+}
+
 // Pinned staging of a batch's inputs (test points, prior mean) and outputs (fmu, fs2).  The callers' arrays are pageable: an
 // "asynchronous" copy from / to them is staged by the runtime's host threads, i.e. the DEVICE timeline of a predict call hangs on
 // the host's scheduling.  Seen on the GPU boxes (256 cores visible, 16 granted): the reference's host code around the call woke a
@@ -191,7 +231,7 @@ static int predict_batch_product(pgp_ctx* c, pgp_factor* f, const CovSpec& cp, c
 // 32768 ... 98304 points, either form -- took 99 ms on the device timeline (34 ... 98 ms of kernels); rounds 3-5 read that as "a
 // hot chip" (tools/_pred_q.py, _pred_t.py; pygps_amd/_threads.py caps the pools).  One memcpy through a pinned buffer of our own
 // (grow-only, per context) keeps the copies true DMA whatever the host is doing.
-static int pred_stage(pgp_ctx* c, size_t doubles) {
+int pred_stage(pgp_ctx* c, size_t doubles) {
     const size_t bytes = doubles * sizeof(double);
     if (c->pred_cap >= bytes) return PGP_OK;
     if (c->pred_host) { (void)hipStreamSynchronize(c->st); (void)hipHostFree(c->pred_host); c->pred_host = nullptr; c->pred_cap = 0; }
@@ -234,9 +274,7 @@ int pgp_predict(pgp_ctx* c, pgp_factor* f, const double* xs, int64_t ns, const d
     // points, ns test points.  It is stored test-major, the orientation of the blocked solve's cross block, so that form serves
     const bool pre = f->cs.has_pre();
     if (pre && (!c->pre1t || !c->pre1s || c->pre_n != n || c->pre_ns != ns || c->pre_ld != np)) return -15;
-    // dot-product leaves: k(z,z) differs per test point too -- the blocked solve with the vector taken from the batch's coordinates
-    const bool dotk = f->cs.has_dot();
-    const bool product = !pre && !dotk && np >= 1024 && (c->predict_inverse == 2 || (c->predict_inverse == 1 && (f->Linv != nullptr || f->Eraw != nullptr || ns >= 1024)));
+    const bool product = predict_takes_product(c, f, ns);
     if (product) CHK(ensure_linv(c, f));
     else CHK(ensure_wd(c, f));
     // test points per batch (the reference uses 1000): up to predict_batch = 65536 within 16 GiB of scratch, so that the K = 128
@@ -289,23 +327,7 @@ int pgp_predict(pgp_ctx* c, pgp_factor* f, const double* xs, int64_t ns, const d
         } else HIP_TRY(hipMemsetAsync(msd, 0, nb_ * sizeof(double), st));
         CHK(scale_transpose_launch(xd, nb_, d, scd, XcT, ldc, dpad, st));
         if (pre) { cp.pre_cross = c->pre1t + a * c->pre_ld; cp.pre_ld = c->pre_ld; cp.pre_cross_rows = c->pre_nsp - a; }
-        if (product) CHK(predict_batch_product(c, f, cp, XcT, ldc, nb_, nrhs, msd, Ks, Vp, part, o1, o2, st));
-        else {
-        // Ks as column-major (np x nrhs): rows = test points, columns = training points in the tile kernel's view
-        HIP_TRY(hipMemsetAsync(Ks, 0, (size_t)np * nrhs * sizeof(double), st));
-        CHK(cov_rect_launch(XcT, ldc, nb_, f->XsT, np, n, dpad, cp, Ks, np, st));
-        CHK(col_dot_full_launch(Ks, np, n, nb_, f->alpha, msd, o1, st));                  // fmu = ms + Ks' alpha
-        if (f->sWv) CHK(row_scale_launch(Ks, np, n, nrhs, f->sWv, st));                   // EP: sW o Ks
-        CHK(solve_lower_multi(c, f->F, f->ldf, f->Wd, Ks, np, np, nrhs, false));
-        if (pre) {                               // k(z,z) differs per test point: raw sums of squares, then max(k_jj - s_j, 0)
-            CHK(col_sumsq_launch(Ks, np, n, nb_, 0.0, -(f->sWv ? 1.0 : f->sw * f->sw), o2, st));
-            CHK(cov_self_vec_launch(cp, 2, c->pre1s + a, 1, nb_, o2, 1, st));
-        } else if (dotk) {
-            CHK(col_sumsq_launch(Ks, np, n, nb_, 0.0, -(f->sWv ? 1.0 : f->sw * f->sw), o2, st));
-            CHK(cov_self_dot_launch(cp, 2, XcT, ldc, dpad, nb_, o2, 1, st));
-        } else
-        CHK(col_sumsq_launch(Ks, np, n, nb_, f->kss, f->sWv ? 1.0 : f->sw * f->sw, o2, st));
-        }
+        CHK(predict_batch(c, f, cp, product, a, XcT, ldc, nb_, nrhs, msd, Ks, Vp, part, o1, o2, st));
         HIP_TRY(hipMemcpyAsync(h_o1, o1, nb_ * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(h_o2, o2, nb_ * sizeof(double), hipMemcpyDeviceToHost, st));
         if (a + NSB >= ns) HIP_TRY(hipEventRecord(c->ev[1], st));

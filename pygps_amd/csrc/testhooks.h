@@ -62,6 +62,14 @@ int pgp_test_vote(pgp_ctx* ctx, const double* fmu, const double* fs2, int64_t ns
 /* the device's yield table (capi.hip: one per device, shared by every context on it; 4096 words, one per CU key) read back to
    out4096 once the context's own streams are idle.  Reads only, launches nothing.  -2: the context has no table */
 int pgp_test_yield_table(pgp_ctx* ctx, uint32_t* out4096);
+/* step 1 of pgp_predict_joint (csrc/joint.hip) alone: V = L^-1 (sW o Ks) for the ns points as one batch, read back.  product_out:
+   1 = the product form, 0 = the blocked solve; nonzero_out (3): entries that are not exact zeros in the padding rows n .. np of the
+   live columns, in the padding columns ns .. nsp, and in the live part */
+int pgp_test_joint_vpad(pgp_ctx* ctx, pgp_factor* f, const double* xs, int64_t ns, int* product_out, int64_t* nonzero_out);
+/* out9: idle bytes of the factor pool and of the scratch pool, their buffer counts, whether the handle f (may be NULL) holds
+   Wd, Linv, the fit's inverse rows, and the scratch-pool bytes and buffers that are OUT (taken by a call or held by a posterior
+   handle, not yet given back: a call that leaks scratch leaves them above their value before it).  Reads host state only. */
+int pgp_test_pool_state(pgp_ctx* ctx, pgp_factor* f, int64_t* out9);
 #ifdef __cplusplus
 }
 #endif

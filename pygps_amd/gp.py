@@ -189,6 +189,141 @@ class GP(object):
         """Same with an explicitly given posterior (Core/gp.py:441-527)."""
         return self._predict(post, xs, ys)
 
+    # ---- the joint posterior: covariances between test points, and draws (no reference counterpart) -----------------
+    def _noise_var(self, noise):
+        if not noise:
+            return 0.0
+        if not isinstance(self.likfunc, lik.Gauss):
+            raise Exception("noise=True adds the Gaussian noise variance sn2 and exists for lik.Gauss only; this model's "
+                            "likelihood is %s" % type(self.likfunc).__name__)
+        return float(np.exp(2.0 * self.likfunc.hyp[0]))
+
+    @staticmethod
+    def _draws(ns, nsamples, rng, z):
+        """The (ns, nsamples) standard normal draws: `z` as given, else from `rng` (a Generator or a seed) on the host."""
+        if z is not None:
+            z = _lib.f64(z)
+            if z.ndim == 1:
+                z = np.ascontiguousarray(z.reshape(ns, 1))
+            if z.ndim != 2 or z.shape[0] != ns or z.shape[1] < 1:
+                raise Exception("z must hold one row of standard normal draws per test point: shape (%d, nsamples)" % ns)
+            return z
+        if int(nsamples) < 1:
+            raise Exception("nsamples must be at least 1")
+        if not isinstance(rng, np.random.Generator):
+            rng = np.random.default_rng(rng)
+        return _lib.f64(rng.standard_normal((ns, int(nsamples))))
+
+    @staticmethod
+    def _check_ns(ns):
+        if ns < 1 or ns > _lib.JOINT_MAX_POINTS:
+            raise Exception("the joint posterior is formed for 1 to %d test points at once; got %d" % (_lib.JOINT_MAX_POINTS, ns))
+
+    @staticmethod
+    def _check_joint(rc, what):
+        if rc > 0:
+            raise np.linalg.LinAlgError("joint covariance not positive definite: first bad pivot %d; pass a larger jitter" % rc)
+        # the point count is the fourth argument of pgp_predict_joint, the fifth of pgp_predict_joint_dense, the third of pgp_sample_mvn
+        count = {"pgp_predict_joint": -4, "pgp_predict_joint_dense": -5, "pgp_sample_mvn": -3}[what]
+        _lib.check(rc, what, {count: "the joint posterior is formed for 1 to %d test points at once" % _lib.JOINT_MAX_POINTS,
+                              -8: "draws need z with at least one column",
+                              -13: "cov.Pre carries no k(xs, xs): the joint posterior is not defined for it"})
+
+    def _joint(self, post, xs, noise, jitter, z, want_cov, want_chol):
+        """fmu (ns, 1), fcov | None, Lc | None, F | None, jitter through the route `predict` takes for this posterior."""
+        L = post.L
+        if getattr(post, "fitc", None) is not None:
+            raise NotImplementedError("pygps_amd: the joint predictive covariance of a FITC posterior is not built")
+        if type(L).__name__ == "DistributedFactor":
+            raise NotImplementedError("pygps_amd: the joint predictive covariance of a sharded posterior is not built")
+        if not isinstance(L, inf.DeviceFactor):
+            raise NotImplementedError("pygps_amd: predict_joint needs a posterior produced by pygps_amd inference "
+                                      "(device-resident factor); there is no CPU fallback")
+        if self.covfunc._pre_leaves():
+            raise NotImplementedError("pygps_amd: a tree with a cov.Pre leaf carries no k(xs, xs); its joint posterior is not built")
+        xs = _lib.f64(_col(xs))
+        ns = xs.shape[0]
+        self._check_ns(ns)
+        sn2 = self._noise_var(noise)
+        ms = _lib.f64(self.meanfunc.getMean(xs)).reshape(ns)
+        dense = bool(getattr(L, "dense", False))
+        Ks = Kss = None
+        if dense:
+            Ks = _lib.f64(self.covfunc.getCovMatrix(x=self.x, z=xs, mode="cross"))
+            Kss = np.array(self.covfunc.getCovMatrix(x=xs, mode="train"), dtype=np.float64, order="C")
+            Kss[np.diag_indices(ns)] = np.asarray(self.covfunc.getCovMatrix(z=xs, mode="self_test"), dtype=np.float64).reshape(ns)
+        if jitter is None:
+            if noise:
+                jitter = 0.0
+            else:
+                kss = Kss.diagonal() if dense else np.asarray(self.covfunc.getCovMatrix(z=xs, mode="self_test")).reshape(ns)
+                jitter = 1e-8 * float(np.mean(kss))
+        jitter = float(jitter)
+        fmu = np.empty(ns)
+        fcov = np.empty((ns, ns)) if want_cov else None
+        Lc = np.empty((ns, ns)) if want_chol else None
+        F = np.empty((ns, z.shape[1])) if z is not None else None
+        nsamp = z.shape[1] if z is not None else 0
+        dll = _lib.load()
+        if dense:
+            rc = dll.pgp_predict_joint_dense(L.ctx, L.handle, _lib.ptr(Ks), _lib.ptr(Kss), ns, _lib.ptr(ms), sn2, jitter, _lib.ptr(z),
+                                             nsamp, _lib.ptr(fmu), _lib.ptr(fcov), _lib.ptr(Lc), _lib.ptr(F), None)
+            self._check_joint(rc, "pgp_predict_joint_dense")
+        else:
+            rc = dll.pgp_predict_joint(L.ctx, L.handle, _lib.ptr(xs), ns, _lib.ptr(ms), sn2, jitter, _lib.ptr(z), nsamp,
+                                       _lib.ptr(fmu), _lib.ptr(fcov), _lib.ptr(Lc), _lib.ptr(F), None)
+            self._check_joint(rc, "pgp_predict_joint")
+        return fmu.reshape(ns, 1), fcov, Lc, F, jitter
+
+    def predict_joint(self, xs, noise=False):
+        """fmu (ns, 1), fcov (ns, ns) = predict_joint(xs): the joint posterior of the latent f at the test points,
+        fcov = Kss - V'V with V = L^-1 (sW o Ks), formed on the device.  diag(fcov) is `predict`'s fs2 (clipped at 0 like it, the
+        off-diagonal entries untouched) and fcov is exactly symmetric.  noise=True (lik.Gauss only) adds sn2 to the diagonal: the
+        covariance of y.  Up to 16384 test points per call.  Exact, EP and Laplace posteriors; FITC, sharded posteriors and trees
+        with a cov.Pre leaf raise NotImplementedError."""
+        sn2 = self._noise_var(noise)                       # (refuses a likelihood without a noise variance before any device work)
+        if self.posterior is None:
+            self.getPosterior()
+        fmu, fcov, _, _, _ = self._joint(self.posterior, xs, False, 0.0, None, True, False)
+        if sn2:
+            fcov[np.diag_indices(fcov.shape[0])] += sn2
+        return fmu, fcov
+
+    def sample_posterior(self, xs, nsamples=1, rng=None, z=None, noise=False, jitter=None, return_chol=False):
+        """F (ns, nsamples) = sample_posterior(xs, nsamples): draws F = fmu 1' + Lc z from the joint posterior at xs, with
+        Lc Lc' = fcov + (noise + jitter) I factorised on the device.  z (ns, nsamples): the standard normal draws to use; otherwise
+        they come from `rng` (an np.random.Generator or a seed; default np.random.default_rng()) on the host.  noise=True
+        (lik.Gauss only) draws y instead of the latent f.  jitter=None means 1e-8 * mean(diag Kss) for latent draws -- the
+        convention of other fp64 GP libraries -- and 0 with noise=True; jitter=0.0 is allowed.  A covariance that is not
+        numerically positive definite raises numpy.linalg.LinAlgError naming the pivot.  return_chol=True returns
+        (F, Lc, fmu, jitter) with the lower factor Lc, exact zeros above its diagonal."""
+        self._noise_var(noise)
+        if self.posterior is None:
+            self.getPosterior()
+        xs = _col(xs)
+        z = self._draws(xs.shape[0], nsamples, rng, z)
+        fmu, _, Lc, F, jitter = self._joint(self.posterior, xs, noise, jitter, z, False, return_chol)
+        return (F, Lc, fmu, jitter) if return_chol else F
+
+    def sample_prior(self, xs, nsamples=1, rng=None, z=None, jitter=None, return_chol=False):
+        """F (ns, nsamples) = sample_prior(xs, nsamples): draws m(xs) 1' + Lc z from the prior, Lc Lc' = k(xs, xs) + jitter I
+        ('train' mode) factorised on the device; needs no data.  z, rng, jitter, return_chol as `sample_posterior`."""
+        xs = _lib.f64(_col(xs))
+        ns = xs.shape[0]
+        self._check_ns(ns)
+        z = self._draws(ns, nsamples, rng, z)
+        K = _lib.f64(self.covfunc.getCovMatrix(x=xs, mode="train"))
+        ms = _lib.f64(self.meanfunc.getMean(xs)).reshape(ns)
+        if jitter is None:
+            jitter = 1e-8 * float(np.mean(K.diagonal()))
+        jitter = float(jitter)
+        F = np.empty((ns, z.shape[1]))
+        Lc = np.empty((ns, ns)) if return_chol else None
+        rc = _lib.load().pgp_sample_mvn(_lib.ctx(), _lib.ptr(K), ns, _lib.ptr(ms), jitter, _lib.ptr(z), z.shape[1], _lib.ptr(Lc),
+                                        _lib.ptr(F))
+        self._check_joint(rc, "pgp_sample_mvn")
+        return (F, Lc, ms.reshape(ns, 1), jitter) if return_chol else F
+
 
 class GPR(GP):
     """Gaussian-process regression: Zero mean, RBF, Gauss likelihood, Exact inference, Minimize."""
