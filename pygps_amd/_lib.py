@@ -154,6 +154,7 @@ TEST_SIGNATURES = {
     "pgp_test_yield_table": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     "pgp_test_joint_vpad": (C.c_int, [_vp, _vp, _dp, _i64, C.POINTER(C.c_int), C.POINTER(_i64)]),
     "pgp_test_pool_state": (C.c_int, [_vp, _vp, C.POINTER(_i64)]),
+    "pgp_test_read_binv": (C.c_int, [_vp, _i64, _dp]),
 }
 
 _lock = threading.RLock()

@@ -70,6 +70,10 @@ int pgp_test_joint_vpad(pgp_ctx* ctx, pgp_factor* f, const double* xs, int64_t n
    Wd, Linv, the fit's inverse rows, and the scratch-pool bytes and buffers that are OUT (taken by a call or held by a posterior
    handle, not yet given back: a call that leaks scratch leaves them above their value before it).  Reads host state only. */
 int pgp_test_pool_state(pgp_ctx* ctx, pgp_factor* f, int64_t* out9);
+/* B^-1 as the last want = 3 fit on this context left it in the workspace (lower triangle, leading dimension ws_np), mirrored into a
+   symmetric row-major (n, n) host matrix once the context's streams are idle.  Reads only, launches nothing but the copy.
+   -3: n rounded up to 128 is not the workspace's size */
+int pgp_test_read_binv(pgp_ctx* ctx, int64_t n, double* out);
 #ifdef __cplusplus
 }
 #endif

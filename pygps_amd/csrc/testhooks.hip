@@ -890,3 +890,22 @@ extern "C" int pgp_test_yield_table(pgp_ctx* c, uint32_t* out4096) {
     HIP_TRY(hipMemcpy(out4096, c->yield_flags, 4096 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return PGP_OK;
 }
+
+// self-test hook: B^-1 as the last want = 3 fit on this context left it in the workspace (c->Binv: column-major, leading dimension
+// ws_np, lower triangle current), mirrored into a symmetric row-major (n, n) host matrix once the context's streams have drained.
+// Reads only, launches nothing but the copy.  -3: the workspace is not sized for this n
+extern "C" int pgp_test_read_binv(pgp_ctx* c, int64_t n, double* out) {
+    if (!c) return -1;
+    if (!out) return -3;
+    GateShared device_gate_hold(c);
+    if (n <= 0 || !c->Binv || round_up(n, 128) != c->ws_np) return -3;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->st));
+    if (c->st2) HIP_TRY(hipStreamSynchronize(c->st2));
+    const long ld = c->ws_np;
+    std::vector<double> h((size_t)ld * n);
+    HIP_TRY(hipMemcpy(h.data(), c->Binv, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (long j = 0; j < n; ++j)
+        for (long i = j; i < n; ++i) out[i * n + j] = out[j * n + i] = h[(size_t)i + (size_t)j * ld];
+    return PGP_OK;
+}

@@ -428,13 +428,14 @@ def ard_slots(kind, D, h0=0):
     return ard_slots(kind[1], D, h0) + ard_slots(kind[2], D, h0 + _nhyp(kind[1], D))
 
 
-def hadamard_ref(kind, hyp, para, x, Binv, alpha, wv=None, sn2=1.0, compat=False, gram=False, centred=False):
+def hadamard_ref(kind, hyp, para, x, Binv, alpha, wv=None, sn2=1.0, compat=False, gram=False, centred=False, return_dks=False):
     """Reference of the fits' gradient pass: for every hyper h, sum_ij Q_ij dK_h,ij with Q = Binv o (w w') - alpha alpha'
     (w = wv; without wv 1/sn2 on the rows, 1 on the columns as in the exact fit), in long double, then sn2 tr(Q).  Per
     component the bar C EPS L sum_ij (|Binv w w'| + |alpha alpha'|)_ij |dK_h,ij| + sum_ij |Q_ij| bar(dK_h)_ij, L = 2 + log2(n^2)
     for the depth of the device's reduction tree.  gram: K weights the sums in the Gram form (dK bars with the centred norms);
     centred: the per-coordinate ARD sums run in the product form on centred coordinates (grad.hip ard_dim_reduce), adding
-    C EPS L sum_ij |Q_ij| |w_ij| 2 (x~_ik^2 + x~_jk^2) with |w| <= |dK / d log sf| / 2 of the leaf."""
+    C EPS L sum_ij |Q_ij| |w_ij| 2 (x~_ik^2 + x~_jk^2) with |w| <= |dK / d log sf| / 2 of the leaf.
+    return_dks: also the dict {h: dK_h} of the long-double derivative matrices the sums were taken against."""
     n, D = x.shape
     nh = O.n_cov_hyp(kind, D)
     B = _ld(Binv)
@@ -466,6 +467,8 @@ def hadamard_ref(kind, hyp, para, x, Binv, alpha, wv=None, sn2=1.0, compat=False
                 bars[h0 + k] += C * EPS * L * 2 * float(np.sum(wgt * (xt2[:, k][:, None] + xt2[:, k][None, :])))
     sums[nh] = LD(sn2) * np.trace(Q)
     bars[nh] = C * EPS * L * float(sn2) * float(np.sum(np.diag(rQ))) + TINY
+    if return_dks:
+        return sums, bars, dks
     return sums, bars
 
 
