@@ -174,6 +174,30 @@ int pgp_exact_fit(pgp_ctx* ctx, int kind, const double* covhyp, int ncov, int pa
                   const double* mvec, const double* dm, int nmean, int want, double* alpha_out, double* nlZ_out,
                   double* dnlZ_out, pgp_factor** factor_out);
 
+/* ---- leave-one-out inference (csrc/loo.hip; GPML's infLOO, Rasmussen & Williams 5.4.2; no reference counterpart) ---------
+ * The exact fit's stages up to B^-1 = E E' (B = K/sn2 + I) and alpha, its posterior (alpha, factor handle: pgp_predict and the
+ * joint / sampling entry points work on it unchanged), then with Kinv = B^-1 / sn2, c_i = Kinv_ii:
+ *      loo_mu_i = y_i - alpha_i / c_i     loo_s2_i = 1 / c_i (noise included)     loo_lp_i = log N(y_i | loo_mu_i, loo_s2_i)
+ *      nlZ_out[0] = nlZ_loo = -sum loo_lp_i          nlZ_out[1] = the marginal nlZ of pgp_exact_fit
+ *      dnlZ_out (nmean + ncov + 1, want = 3) = the gradient of nlZ_loo: 1/2 sum(Q_loo o dK_h), sn2 tr Q_loo, -u' dm_h with
+ *      w_i = (1 + alpha_i^2 / c_i) / (2 c_i), u = Kinv (alpha / c), Q_loo = 2 Kinv diag(w) Kinv - u alpha' - alpha u'
+ * want: 1 = posterior only (no LOO output), 2 = plus the values, 3 = plus the gradient.  loo_*_out (n each) may be NULL.
+ * want = 2 runs nothing O(n^3) beyond the factorisation: diag(B^-1) is read off the fused inverse rows; want = 3 reads the same
+ * sums, so both return the same bits.  With the fused inverse switched off or refused (options fused_inverse 0,
+ * fused_value_max_np; no scratch) a want = 2 call takes want = 3's route to B^-1 instead (triangular inverse + W'W), and its alpha
+ * is that route's (W'z), equal to pgp_exact_fit's want = 2 alpha (back-substitution) to rounding only.
+ * pgp_loo_fit_dense: the same from a caller-built K (as pgp_exact_fit_dense); only r = y - m is handed in, so loo_mu_out is
+ * r_i - alpha_i / c_i: THE CALLER ADDS m BACK.  u_out (n, want = 3, may be NULL): the mean gradients are -u' dm_h, formed by the
+ * caller.  After want = 3 the workspace holds sn2 Q_loo and a zero alpha: pgp_dense_grad_term(ctx, dK_h, n, log_sn, &g) directly
+ * afterwards returns 1/2 sum(Q_loo o dK_h).
+ * Out of scope: EP / Laplace cavity LOO, FITC, sharded fits.  Status as pgp_exact_fit / pgp_exact_fit_dense. */
+int pgp_loo_fit(pgp_ctx* ctx, int kind, const double* covhyp, int ncov, int para, int flags, double log_sn, const double* mvec,
+                const double* dm, int nmean, int want, double* alpha_out, double* loo_mu_out, double* loo_s2_out,
+                double* loo_lp_out, double* nlZ_out, double* dnlZ_out, pgp_factor** factor_out);
+int pgp_loo_fit_dense(pgp_ctx* ctx, const double* K, int64_t n, const double* r, double log_sn, int want, double* alpha_out,
+                      double* loo_mu_out, double* loo_s2_out, double* loo_lp_out, double* nlZ_out, double* dnlZ_lik_out,
+                      double* u_out, pgp_factor** factor_out);
+
 /* post.L as numpy expects it: (n,n) row-major UPPER factor, exact zeros below the diagonal
  * (Core/gp.py:393 branches on that).                                                           */
 int pgp_factor_to_host(pgp_ctx* ctx, pgp_factor* f, double* L_out);

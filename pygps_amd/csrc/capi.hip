@@ -163,6 +163,7 @@ void pgp_destroy(pgp_ctx* c) { if (!c) return; GateShared device_gate_hold(c);
     if (c->res_host) (void)hipHostFree(c->res_host);
     if (c->in_host) (void)hipHostFree(c->in_host);
     if (c->pred_host) (void)hipHostFree(c->pred_host);
+    if (c->loo_host) (void)hipHostFree(c->loo_host);
     if (c->gemm_trace) (void)hipFree(c->gemm_trace);
     for (auto& e : c->ev) (void)hipEventDestroy(e);
     for (auto& e : c->ev_pool) (void)hipEventDestroy(e);
@@ -971,9 +972,18 @@ int pgp_set_data(pgp_ctx* c, const double* x, int64_t n, int64_t d, const double
     return PGP_OK;
 }
 
-int pgp_exact_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para, int flags, double log_sn,
-                  const double* mvec, const double* dm, int nmean, int want, double* alpha_out, double* nlZ_out,
-                  double* dnlZ_out, pgp_factor** factor_out) {
+}  // extern "C"
+
+// Exact.evaluate, and with `loo` its leave-one-out variant (loo.hip): the same stages up to B^-1 and alpha, the same posterior;
+// the LOO tail then replaces B^-1 by S = sn2 Q_loo and hands the gradient pass a zero vector for alpha.  nlZ_out receives the
+// marginal likelihood either way (loo->nlZ_loo the LOO objective); dnlZ_out the gradient of the one the call is about.
+// A value-only LOO call (want < 3) reads diag(B^-1) off the fused inverse rows (row sums of squares of E) and runs nothing
+// O(n^3) beyond the factorisation; want = 3 reads the SAME sums, so that both return the same bits.  Where the fused inverse is
+// switched off or refused (fused_inverse 0, fused_value_max_np, no scratch), a value-only LOO call takes want = 3's route to
+// B^-1 (triangular inverse + W'W) and reads its diagonal.
+static int exact_fit_run(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para, int flags, double log_sn,
+                         const double* mvec, const double* dm, int nmean, int want, double* alpha_out, double* nlZ_out,
+                         double* dnlZ_out, pgp_factor** factor_out, LooOut* loo) {
     if (!c) return -1;
     GateShared device_gate_hold(c);
     if (!c) return -1;
@@ -1001,7 +1011,7 @@ int pgp_exact_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para
     double kss = 0.0;
     if (factor_out && !cp.has_dot()) CHK(cov_point_value(c, cp, 2, &kss));      // (dot-product leaves: predict takes k(z,z) per point)
     const long need = std::max(hadamard_partial_count(np, ncov), 32L * np);       // also the partials of upper_matvec
-    if ((want >= 3 || fused) && c->partial_cap < need) {
+    if ((want >= 3 || fused || loo) && c->partial_cap < need) {
         if (c->partial) (void)hipFree(c->partial);
         c->partial = nullptr; c->partial_cap = 0;      // a failed realloc must not leave a dangling pointer behind
         HIP_TRY(hipMalloc((void**)&c->partial, need * sizeof(double)));
@@ -1021,6 +1031,7 @@ int pgp_exact_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para
             (void)hipGetLastError(); fused = false; E = nullptr;      // value-only: the plain sweep needs no inverse rows
         }
     }
+    const int rwant = (loo && want >= 2 && !fused) ? 3 : want;    // the route to B^-1 and alpha (see above); == want for every plain fit
     hipStream_t st = c->st;
     HIP_TRY(hipMemsetAsync(c->info_dev, 0, sizeof(int), st));
     if (mvec) {                                      // through pinned memory: an async copy from pageable memory is staged
@@ -1055,7 +1066,7 @@ int pgp_exact_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para
         HIP_TRY(hipEventRecord(c->ev[3], st));
         { ProfScope ps(c, PC_SMALL, 0.0, 4.0 * (double)np * np);                      // alpha = W^T z / sn2 = E z / sn2
           CHK(upper_matvec_launch(E, lde, np, c->zvec, 1.0 / sn2, c->partial, c->alpha_dev, st)); }
-    } else if (want >= 3) {
+    } else if (rwant >= 3) {
         CHK(trtri_lower(c, F, ldf, c->W, np, c->T, np));
         HIP_TRY(hipEventRecord(c->ev[3], st));
         { ProfScope ps(c, PC_SMALL, 0.0, 4.0 * (double)np * np);
@@ -1069,19 +1080,35 @@ int pgp_exact_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para
     }
     HIP_TRY(hipEventRecord(c->ev[4], st));
     // ---- S5b: B^-1 = W^T W ; S6: gradient reduce ------------------------------------------------
-    if (want >= 3) {
+    double* lbuf = nullptr;                          // LOO: [mu | s2 | lp | u | nlZ_loo ...] and the tail's device-only vectors
+    if (rwant >= 3) {
         if (fused && job.join) HIP_TRY(hipStreamWaitEvent(st, job.join, 0));        // accumulated under the sweep
         else if (fused) CHK(eet_lower(c, E, lde, c->Binv, np, np));                   // B^-1 = W^T W = E E^T
         else CHK(lauum_lower(c, c->W, np, c->Binv, np, np));
-        HIP_TRY(hipEventRecord(c->ev[5], st));
-        // alpha currently holds W^T z / sn2 = B^-1 r / sn2  (already the final alpha)
-        { ProfScope ps(c, PC_HADAMARD, 0.0, 8.0 * (double)np * (np + 1) / 2.0 + 8.0 * (double)n * d);
-          CHK(hadamard_reduce_launch(c->XsT, np, n, np, c->dpad, cp, ncov, sn2, c->Binv, np, c->alpha_dev, c->partial,
-                                     c->scal + 8, st, nullptr, gram ? c->prep : nullptr)); }
-    } else {
-        HIP_TRY(hipEventRecord(c->ev[5], st));
+    }
+    HIP_TRY(hipEventRecord(c->ev[5], st));
+    // alpha currently holds W^T z / sn2 = B^-1 r / sn2  (already the final alpha)
+    const double* grad_alpha = c->alpha_dev;
+    if (loo && want >= 2) {
+        CHK(pscr.alloc(&lbuf, (size_t)loo_buffer_doubles(np) * sizeof(double)));
+        CHK(loo_values_launch(c, n, np, sn2, fused ? E : nullptr, lde, c->y_dev, c->alpha_dev, c->partial, lbuf, st));
+        if (want >= 3) {
+            double *G = c->W, *svp = nullptr;        // W is free once W'W is formed; beside the fused inverse it was never used
+            if (fused) CHK(pscr.alloc(&G, (size_t)np * np * sizeof(double)));         // (E goes on to the posterior handle)
+            CHK(pscr.alloc(&svp, (size_t)loo_symv_partial_doubles(np) * sizeof(double)));
+            HIP_TRY(hipMemsetAsync(loo_vec(lbuf, np, LOO_ZERO), 0, np * sizeof(double), st));
+            CHK(loo_gradient_matrix(c, n, np, sn2, c->alpha_dev, lbuf, G, svp, st));   // c->Binv <- S = sn2 Q_loo
+            grad_alpha = loo_vec(lbuf, np, LOO_ZERO);
+        }
+        CHK(loo_stage(c, (size_t)loo_host_doubles(np)));
+    }
+    if (want >= 3) {
+        ProfScope ps(c, PC_HADAMARD, 0.0, 8.0 * (double)np * (np + 1) / 2.0 + 8.0 * (double)n * d);
+        CHK(hadamard_reduce_launch(c->XsT, np, n, np, c->dpad, cp, ncov, sn2, c->Binv, np, grad_alpha, c->partial,
+                                   c->scal + 8, st, nullptr, gram ? c->prep : nullptr));
     }
     HIP_TRY(hipEventRecord(c->ev[6], st));
+    if (lbuf) HIP_TRY(hipMemcpyAsync(c->loo_host, lbuf, (size_t)loo_host_doubles(np) * sizeof(double), hipMemcpyDeviceToHost, st));   // pinned: queued, not staged
     // ---- results to host: ONE copy of [scalars | status | alpha] into pinned memory ---------------------
     // (round 6) the LAST KERNEL of the fit writes them into the pinned buffer through its device-side address: a copy command
     // behind the last kernel cost a lone chain ~100 us (final_reduce's end to the copy's start in the kernel trace); option publish = 0
@@ -1092,7 +1119,7 @@ int pgp_exact_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para
     double* alpha_h = c->res_host + RES_HEAD;
     int info = 0;
     memcpy(&info, c->res_host + RES_INFO, sizeof(int));
-    if (want < 3 && !fused) for (long j = 0; j < n; ++j) alpha_h[j] /= sn2;   // the back-substitution produced L^-T z
+    if (rwant < 3 && !fused) for (long j = 0; j < n; ++j) alpha_h[j] /= sn2;   // the back-substitution produced L^-T z
     {
         float ms;
         const int map[6][2] = {{0, 1}, {1, 2}, {3, 4}, {2, 3}, {4, 5}, {5, 6}};   // assemble, potrf, solve, trtri, lauum, grad
@@ -1106,10 +1133,19 @@ int pgp_exact_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para
         const double logdet = sc_host[0], ztz = sc_host[1];
         *nlZ_out = 0.5 * ztz / sn2 + logdet + 0.5 * (double)n * log(2.0 * M_PI * sn2);
     }
+    if (lbuf) {
+        const double* v = c->loo_host;
+        if (loo->mu) memcpy(loo->mu, v + LOO_MU * np, n * sizeof(double));
+        if (loo->s2) memcpy(loo->s2, v + LOO_S2 * np, n * sizeof(double));
+        if (loo->lp) memcpy(loo->lp, v + LOO_LP * np, n * sizeof(double));
+        if (loo->u && want >= 3) memcpy(loo->u, v + LOO_U * np, n * sizeof(double));
+        loo->nlZ_loo = v[LOO_HOST_VECS * np];
+    }
     if (want >= 3 && dnlZ_out) {
+        const double* gv = lbuf ? c->loo_host + LOO_U * np : alpha_h;        // LOO: -u' dm_h takes the place of -alpha' dm_h
         for (int i = 0; i < nmean; ++i) {                 // Core/inf.py:378-381
             double s = 0.0;
-            for (long j = 0; j < n; ++j) s += dm[(long)i * n + j] * alpha_h[j];
+            for (long j = 0; j < n; ++j) s += dm[(long)i * n + j] * gv[j];
             dnlZ_out[i] = -s;
         }
         for (int h = 0; h < ncov; ++h) dnlZ_out[nmean + h] = 0.5 * sc_host[8 + h];      // inf.py:377
@@ -1136,6 +1172,26 @@ int pgp_exact_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para
     }
     fguard.scrub = false;                             // a finished factor honours the pool contract as it is
     return PGP_OK;
+}
+
+extern "C" {
+
+int pgp_exact_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para, int flags, double log_sn,
+                  const double* mvec, const double* dm, int nmean, int want, double* alpha_out, double* nlZ_out,
+                  double* dnlZ_out, pgp_factor** factor_out) {
+    return exact_fit_run(c, kind, covhyp, ncov, para, flags, log_sn, mvec, dm, nmean, want, alpha_out, nlZ_out, dnlZ_out, factor_out,
+                         nullptr);
+}
+
+int pgp_loo_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para, int flags, double log_sn, const double* mvec,
+                const double* dm, int nmean, int want, double* alpha_out, double* loo_mu_out, double* loo_s2_out, double* loo_lp_out,
+                double* nlZ_out, double* dnlZ_out, pgp_factor** factor_out) {
+    LooOut lo{loo_mu_out, loo_s2_out, loo_lp_out, nullptr, 0.0};
+    double nlz = 0.0;
+    const int rc = exact_fit_run(c, kind, covhyp, ncov, para, flags, log_sn, mvec, dm, nmean, want, alpha_out, &nlz, dnlZ_out,
+                                 factor_out, &lo);
+    if (rc == PGP_OK && want >= 2 && nlZ_out) { nlZ_out[0] = lo.nlZ_loo; nlZ_out[1] = nlz; }
+    return rc;
 }
 
 int64_t pgp_factor_n(pgp_factor* f) { return f ? f->n : 0; }

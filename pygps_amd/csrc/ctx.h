@@ -160,6 +160,8 @@ struct pgp_ctx {
     int publish = 1;                    // option "publish" 1 / 0
     double* in_host = nullptr;          // pinned staging of the per-fit inputs (prior mean, scales)
     double* pred_host = nullptr;        // pinned staging of pgp_predict's inputs and outputs (grow-only: predict.hip pred_stage)
+    double* loo_host = nullptr;         // pinned staging of a LOO fit's [mu | s2 | lp | u | nlZ_loo] (grow-only: loo.hip loo_stage): the copy
+    size_t loo_host_cap = 0;            // into it is queued without blocking the host, in front of the fit's publish kernel
     size_t pred_cap = 0;
     size_t res_cap = 0, in_cap = 0;
     // Cholesky sweep: diagonal-panel scratch (2w x w, w <= 1024), its leaf operand images, column staging buffer
@@ -476,6 +478,23 @@ int ensure_workspace(pgp_ctx* c, long np);
 int solve_lower_multi(pgp_ctx* c, const double* L, long ldl, const double* Wd, double* Y, long ldy, long np, int nrhs,
                       bool trans);
 int eet_lower(pgp_ctx* c, const double* E, long lde, double* Binv, long ldb, long np);
+// ---- leave-one-out tail of the exact fits (loo.hip) ------------------------------------------------------------------------
+// One scratch buffer of loo_buffer_doubles(np): LOO_DEV_VECS vectors of np doubles, then LOO_SCAL scalars -- except that the
+// scalars sit right behind the first LOO_HOST_VECS vectors, so that what the host needs ([mu | s2 | lp | u | nlZ_loo ...]) comes
+// down with one copy of loo_host_doubles(np).
+enum LooVec { LOO_MU = 0, LOO_S2, LOO_LP, LOO_U, LOO_HOST_VECS, LOO_CDIAG = LOO_HOST_VECS, LOO_W, LOO_AOC, LOO_G, LOO_ZERO, LOO_DEV_VECS };
+constexpr long LOO_SCAL = 8;
+static inline double* loo_vec(double* buf, long np, int v) { return buf + (long)v * np + (v >= LOO_HOST_VECS ? LOO_SCAL : 0); }
+static inline long loo_host_doubles(long np) { return LOO_HOST_VECS * np + LOO_SCAL; }
+long loo_buffer_doubles(long np);
+long loo_symv_partial_doubles(long np);
+int loo_stage(pgp_ctx* c, size_t doubles);
+int loo_values_launch(pgp_ctx* c, long n, long np, double sn2, const double* E, long lde, const double* yv, const double* alpha,
+                      double* partial, double* buf, hipStream_t st);
+int loo_gradient_matrix(pgp_ctx* c, long n, long np, double sn2, const double* alpha, double* buf, double* G, double* symv_partial,
+                        hipStream_t st);
+// What a LOO fit hands back beside the exact fit's own results (capi.hip exact_fit_run, dense.hip dense_fit_run); null = plain fit
+struct LooOut { double *mu, *s2, *lp, *u; double nlZ_loo; };
 // predict.hip, shared with joint.hip (pgp_predict_joint): the posterior handle's lazy operands, the pinned staging, the rule that
 // picks the form of V = L^-1 (sW o Ks), and one batch of the prediction in either form
 int ensure_wd(pgp_ctx* c, pgp_factor* f);

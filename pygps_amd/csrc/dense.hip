@@ -69,12 +69,13 @@ __global__ __launch_bounds__(256) void dense_trace_kernel(const double* __restri
 
 }  // namespace
 
-extern "C" {
-
 // r = y - m (n).  K (n,n) symmetric, row-major host.  want as pgp_exact_fit.  dnlZ_lik_out: sn2 tr Q (want = 3).  The inverse
 // B^-1 and alpha stay in the context's workspace for the pgp_dense_grad_term calls that follow directly.
-int pgp_exact_fit_dense(pgp_ctx* c, const double* K, int64_t n, const double* r, double log_sn, int want, double* alpha_out,
-                        double* nlZ_out, double* dnlZ_lik_out, pgp_factor** factor_out) {
+// With `loo` (pgp_loo_fit_dense; loo.hip): the leave-one-out values from the fused inverse rows at every want >= 2, and at
+// want = 3 the workspace is left holding S = sn2 Q_loo and a ZERO alpha -- alpha goes to the host first -- so that
+// pgp_dense_grad_term returns 1/2 sum(Q_loo o dK) unchanged; dnlZ_lik_out = sn2 tr Q_loo.
+static int dense_fit_run(pgp_ctx* c, const double* K, int64_t n, const double* r, double log_sn, int want, double* alpha_out,
+                         double* nlZ_out, double* dnlZ_lik_out, pgp_factor** factor_out, LooOut* loo) {
     if (!c) return -1;
     GateShared device_gate_hold(c);
     if (!c) return -1;
@@ -85,7 +86,7 @@ int pgp_exact_fit_dense(pgp_ctx* c, const double* K, int64_t n, const double* r,
     HIP_TRY(hipSetDevice(c->device));
     c->dense_ready = false;
     const long np = round_up(n, 128), ldf = np + 128;
-    const bool fused = want >= 3;
+    const bool fused = want >= 3 || (loo && want >= 2);
     CHK(ensure_workspace(c, np));
     const long need = std::max<long>(32L * np, np);
     if (c->partial_cap < need) {
@@ -99,7 +100,7 @@ int pgp_exact_fit_dense(pgp_ctx* c, const double* K, int64_t n, const double* r,
     CHK(alloc_factor_buffer(c, np, ldf, &F));
     FactorGuard fguard(c, F, (size_t)ldf * np * sizeof(double), /*scrub=*/true);
     PoolScratch scr(c);
-    double *Kd = nullptr, *E = nullptr, *zero = nullptr;
+    double *Kd = nullptr, *E = nullptr, *zero = nullptr, *lbuf = nullptr;
     CHK(scr.alloc(&Kd, (size_t)n * n * sizeof(double)));
     CHK(scr.alloc(&zero, (size_t)np * sizeof(double)));
     if (fused) CHK(scr.alloc(&E, (size_t)np * np * sizeof(double)));
@@ -113,7 +114,7 @@ int pgp_exact_fit_dense(pgp_ctx* c, const double* K, int64_t n, const double* r,
                        ldf, np);
     CHK(aug_rhs_launch(c->zvec, zero, n, F, ldf, np, c->rvec, st));
     SweepJob job{F, ldf, np, np + 128, fused, E, np};
-    if (fused) { job.eet_out = c->Binv; job.eet_ld = np; }
+    if (want >= 3) { job.eet_out = c->Binv; job.eet_ld = np; }
     const int prc = potrf_blocked(c, job);
     if (prc != PGP_OK) (void)hipDeviceSynchronize();
     CHK(prc);
@@ -121,17 +122,38 @@ int pgp_exact_fit_dense(pgp_ctx* c, const double* K, int64_t n, const double* r,
     CHK(gather_strided_launch(F + np, ldf, np, c->zvec, st));
     if (fused) {
         CHK(upper_matvec_launch(E, np, np, c->zvec, 1.0 / sn2, c->partial, c->alpha_dev, st));
-        if (job.join) HIP_TRY(hipStreamWaitEvent(st, job.join, 0));
-        else CHK(eet_lower(c, E, np, c->Binv, np, np));
-        hipLaunchKernelGGL(dense_trace_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c->Binv, np, c->alpha_dev, n, sn2,
-                           c->partial);
-        hipLaunchKernelGGL(dense_sum_kernel, dim3(1), dim3(256), 0, st, c->partial, n, 1.0, c->scal + 8);
+        if (want >= 3) {
+            if (job.join) HIP_TRY(hipStreamWaitEvent(st, job.join, 0));
+            else CHK(eet_lower(c, E, np, c->Binv, np, np));
+        }
+        const double* grad_alpha = c->alpha_dev;
+        if (loo) {
+            CHK(scr.alloc(&lbuf, (size_t)loo_buffer_doubles(np) * sizeof(double)));
+            CHK(loo_values_launch(c, n, np, sn2, E, np, c->rvec, c->alpha_dev, c->partial, lbuf, st));      // rvec = r: mu lacks m
+            if (want >= 3) {
+                double *G = nullptr, *svp = nullptr;
+                CHK(scr.alloc(&G, (size_t)np * np * sizeof(double)));
+                CHK(scr.alloc(&svp, (size_t)loo_symv_partial_doubles(np) * sizeof(double)));
+                CHK(loo_gradient_matrix(c, n, np, sn2, c->alpha_dev, lbuf, G, svp, st));                    // c->Binv <- S = sn2 Q_loo
+                grad_alpha = zero;
+            }
+            CHK(loo_stage(c, (size_t)loo_host_doubles(np)));
+        }
+        if (want >= 3) {
+            hipLaunchKernelGGL(dense_trace_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c->Binv, np, grad_alpha, n, sn2,
+                               c->partial);
+            hipLaunchKernelGGL(dense_sum_kernel, dim3(1), dim3(256), 0, st, c->partial, n, 1.0, c->scal + 8);
+        }
     } else {
         CHK(leaf_inv_launch(F, ldf, c->W, np, 128L * (1 + np), (int)(np / 128), st));
         CHK(trsv_bwd_launch(F, ldf, c->W, np, c->zvec, c->alpha_dev, (int)(np / 128), st));
     }
     if (hipGetLastError() != hipSuccess) return PGP_ERR_HIP;
     HIP_TRY(hipMemcpyAsync(c->res_host, c->res_dev, (size_t)(272 + n) * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (lbuf) {
+        HIP_TRY(hipMemcpyAsync(c->loo_host, lbuf, (size_t)loo_host_doubles(np) * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (want >= 3) HIP_TRY(hipMemsetAsync(c->alpha_dev, 0, np * sizeof(double), st));       // behind the copy that took alpha out
+    }
     HIP_TRY(hipStreamSynchronize(st));
     if (c->prof) prof_collect(c);
     int info = 0;
@@ -142,6 +164,14 @@ int pgp_exact_fit_dense(pgp_ctx* c, const double* K, int64_t n, const double* r,
     if (alpha_out) memcpy(alpha_out, alpha_h, n * sizeof(double));
     if (want >= 2 && nlZ_out) *nlZ_out = 0.5 * c->res_host[1] / sn2 + c->res_host[0] + 0.5 * (double)n * log(2.0 * M_PI * sn2);
     if (want >= 3 && dnlZ_lik_out) *dnlZ_lik_out = c->res_host[8];
+    if (lbuf) {
+        const double* v = c->loo_host;
+        if (loo->mu) memcpy(loo->mu, v + LOO_MU * np, n * sizeof(double));
+        if (loo->s2) memcpy(loo->s2, v + LOO_S2 * np, n * sizeof(double));
+        if (loo->lp) memcpy(loo->lp, v + LOO_LP * np, n * sizeof(double));
+        if (loo->u && want >= 3) memcpy(loo->u, v + LOO_U * np, n * sizeof(double));
+        loo->nlZ_loo = v[LOO_HOST_VECS * np];
+    }
     if (factor_out) {
         FactorHandleGuard hg(c, new pgp_factor());
         pgp_factor* f = hg.f;
@@ -156,6 +186,23 @@ int pgp_exact_fit_dense(pgp_ctx* c, const double* K, int64_t n, const double* r,
     fguard.scrub = false;
     if (want >= 3) { c->dense_ready = true; c->dense_n = n; }
     return PGP_OK;
+}
+
+extern "C" {
+
+int pgp_exact_fit_dense(pgp_ctx* c, const double* K, int64_t n, const double* r, double log_sn, int want, double* alpha_out,
+                        double* nlZ_out, double* dnlZ_lik_out, pgp_factor** factor_out) {
+    return dense_fit_run(c, K, n, r, log_sn, want, alpha_out, nlZ_out, dnlZ_lik_out, factor_out, nullptr);
+}
+
+int pgp_loo_fit_dense(pgp_ctx* c, const double* K, int64_t n, const double* r, double log_sn, int want, double* alpha_out,
+                      double* loo_mu_out, double* loo_s2_out, double* loo_lp_out, double* nlZ_out, double* dnlZ_lik_out, double* u_out,
+                      pgp_factor** factor_out) {
+    LooOut lo{loo_mu_out, loo_s2_out, loo_lp_out, u_out, 0.0};
+    double nlz = 0.0;
+    const int rc = dense_fit_run(c, K, n, r, log_sn, want, alpha_out, &nlz, dnlZ_lik_out, factor_out, &lo);
+    if (rc == PGP_OK && want >= 2 && nlZ_out) { nlZ_out[0] = lo.nlZ_loo; nlZ_out[1] = nlz; }
+    return rc;
 }
 
 // out = 1/2 sum_ij Q_ij dK_ij with Q = B^-1 / sn2 - alpha alpha' of the pgp_exact_fit_dense call (want = 3, same n, same log_sn)

@@ -340,13 +340,35 @@ class GPR(GP):
         self.likfunc = lik.Gauss(log_sigma)
 
     def useInference(self, newInf):
-        """'Laplace' or 'EP' (Core/gp.py:611-622)."""
+        """'Laplace' or 'EP' (Core/gp.py:611-622), or 'LOO': the leave-one-out log pseudo-likelihood as the objective of
+        optimize() / getPosterior() (inf.LOO; no reference counterpart)."""
         if newInf == "Laplace":
             self.inffunc = inf.Laplace()
         elif newInf == "EP":
             self.inffunc = inf.EP()
+        elif newInf == "LOO":
+            self.inffunc = inf.LOO()
         else:
-            raise Exception('Possible inf values are "Laplace", "EP".')
+            raise Exception('Possible inf values are "Laplace", "EP", "LOO".')
+
+    def predict_loo(self, x=None, y=None):
+        """ymu, ys2, fmu, fs2, lp = predict_loo([x, y]): the leave-one-out predictive at every training point, each (n, 1) as
+        predict returns them.  Point i is predicted from the other n - 1 with the model's current hyper-parameters, in closed
+        form from one factorisation (inf.LOO; the value-only device call: nothing O(n^3) beyond the factorisation).  ymu / ys2
+        are for the observation y_i (noise included), fmu = ymu, fs2 = ys2 - sn2, lp = log N(y_i | ymu_i, ys2_i).  Works
+        whatever inference the model uses, provided that is Exact or LOO on lik.Gauss on one GPU; EP / Laplace cavity LOO,
+        FITC and sharded fits are out of scope."""
+        self._take_xy(x, y)
+        if not isinstance(self.inffunc, inf.Exact) or not isinstance(self.likfunc, lik.Gauss):
+            raise Exception("predict_loo needs Exact or LOO inference with Gaussian likelihood")
+        loo = inf.LOO()
+        loo.device = self.inffunc.device
+        if getattr(self.inffunc, "sharded", False):
+            raise NotImplementedError("pygps_amd: leave-one-out inference runs on one GPU (no sharded fit)")
+        loo.evaluate(self.meanfunc, self.covfunc, self.likfunc, self.x, self.y, 2)
+        mu, s2, lp = loo.last_loo
+        sn2 = float(np.exp(2.0 * self.likfunc.hyp[0]))
+        return mu, s2, mu.copy(), s2 - sn2, lp
 
     def useLikelihood(self, newLik):
         """'Laplace': lik.Laplace with EP inference (Core/gp.py:624-635)."""

@@ -308,8 +308,7 @@ class Exact(Inference):
         fh = C.c_void_p()
         DeviceFactor.reserve(n, dev)
         want = int(min(max(nargout, 1), 3))
-        _lib.check(lib.pgp_exact_fit_dense(ctx, _lib.ptr(K), n, _lib.ptr(r), log_sn, want, _lib.ptr(alpha), _lib.ptr(nlZ),
-                                           _lib.ptr(glik), C.byref(fh)), "pgp_exact_fit_dense")
+        gvec = self._call_dense(lib, ctx, K, n, r, m, log_sn, want, alpha, nlZ, glik, fh)
         del K
         post = postStruct()
         post.alpha = alpha.reshape(n, 1)
@@ -325,15 +324,29 @@ class Exact(Inference):
                     dK = _lib.f64(covfunc.getDerMatrix(x=x, mode="train", der=h))
                     _lib.check(lib.pgp_dense_grad_term(ctx, _lib.ptr(dK), n, log_sn, _lib.ptr(g)), "pgp_dense_grad_term")
                     dnlZ.cov.append(np.float64(g[0]))
-                dnlZ.mean = [np.float64(-(dm[i] @ alpha)) for i in range(nm)]     # Core/inf.py:378-381
+                dnlZ.mean = [np.float64(-(dm[i] @ gvec)) for i in range(nm)]      # Core/inf.py:378-381
                 dnlZ.lik = [np.float64(glik[0])]
                 return post, np.float64(nlZ[0]), dnlZ
             return post, np.float64(nlZ[0])
         return post
 
+    # the two device calls, as hooks: inf.LOO overrides them (and nothing else of evaluate / _evaluate_dense)
+    def _call_dense(self, lib, ctx, K, n, r, m, log_sn, want, alpha, nlZ, glik, fh):
+        """The dense route's fit; returns the vector v of the mean gradients -v' dm_h (alpha)."""
+        _lib.check(lib.pgp_exact_fit_dense(ctx, _lib.ptr(K), n, _lib.ptr(r), log_sn, want, _lib.ptr(alpha), _lib.ptr(nlZ),
+                                           _lib.ptr(glik), C.byref(fh)), "pgp_exact_fit_dense")
+        return alpha
+
+    def _call_program(self, ctx, kind, hyp, nc, para, flags, log_sn, m, dm, nm, want, n, alpha, nlZ, g, fh):
+        rc = _lib.load().pgp_exact_fit(ctx, kind, _lib.ptr(hyp), nc, int(para), int(flags), log_sn, _lib.ptr(m), _lib.ptr(dm), nm,
+                                       want, _lib.ptr(alpha), _lib.ptr(nlZ), _lib.ptr(g), C.byref(fh))
+        _lib.check(rc, "pgp_exact_fit")
+
+    _gauss_only = "Exact inference only possible with Gaussian likelihood"
+
     def evaluate(self, meanfunc, covfunc, likfunc, x, y, nargout=1):
         if not isinstance(likfunc, _lik.Gauss):
-            raise Exception("Exact inference only possible with Gaussian likelihood")
+            raise Exception(self._gauss_only)
         if self.sharded:
             _cov.refuse_pre(covfunc, "a sharded fit (the panels of a distributed factor are assembled per rank)")
             _cov.refuse_dot(covfunc, "a sharded fit")
@@ -359,10 +372,8 @@ class Exact(Inference):
         nlZ = np.zeros(1)
         g = np.zeros(nm + nc + 1)
         fh = C.c_void_p()
-        rc = _lib.load().pgp_exact_fit(_lib.ctx(dev), kind, _lib.ptr(hyp), nc, int(para), int(flags), log_sn,
-                                       _lib.ptr(m), _lib.ptr(dm), nm, int(min(max(nargout, 1), 3)), _lib.ptr(alpha),
-                                       _lib.ptr(nlZ), _lib.ptr(g), C.byref(fh))
-        _lib.check(rc, "pgp_exact_fit")
+        self._call_program(_lib.ctx(dev), kind, hyp, nc, para, flags, log_sn, m, dm, nm, int(min(max(nargout, 1), 3)), n, alpha,
+                           nlZ, g, fh)
         sn2 = np.exp(2 * log_sn)
         post = postStruct()
         post.alpha = alpha.reshape(n, 1)
@@ -378,6 +389,59 @@ class Exact(Inference):
                 return post, nlz, dnlZ
             return post, nlz
         return post
+
+
+class LOO(Exact):
+    """Leave-one-out inference for a Gaussian likelihood (GPML's infLOO; Rasmussen & Williams 5.4.2; the reference has none).
+
+    The posterior is the exact fit's own -- predict, predict_joint and the samplers work on it unchanged; bit for bit where both
+    take the same route to alpha: always with gradients, value-only with the fused inverse (the default) -- but ``nlZ`` is the
+    negative LOO log pseudo-likelihood -sum_i log p(y_i | x, y_-i, hyp) and ``dnlZ`` its gradient (mean | cov | lik), both
+    in closed form from the one factorisation (pgp_loo_fit, csrc/loo.hip; pgp_loo_fit_dense for covariance trees that are not
+    device programs).  After every evaluate with nargout >= 2: ``last_loo = (mu, s2, lp)``, each (n, 1) -- the LOO
+    predictive mean, variance (noise included) and log density of every training point -- and ``last_nlZ_marginal``.
+
+    Out of scope: EP / Laplace cavity LOO (lik.Gauss only), FITC, sharded fits."""
+
+    def __init__(self, sharded=False):
+        super(LOO, self).__init__(sharded=sharded)
+        self.name = "Leave-one-out inference"
+        self.last_loo = None
+        self.last_nlZ_marginal = None
+
+    _gauss_only = "LOO inference only possible with Gaussian likelihood"
+
+    def _keep(self, n, mu, s2, lp, nlz2, want):
+        if want > 1:
+            self.last_loo = (mu.reshape(n, 1), s2.reshape(n, 1), lp.reshape(n, 1))
+            self.last_nlZ_marginal = np.float64(nlz2[1])
+
+    def _call_dense(self, lib, ctx, K, n, r, m, log_sn, want, alpha, nlZ, glik, fh):
+        """pgp_loo_fit_dense: the device is handed r = y - m only, so m is added back to the LOO means here; the covariance
+        gradients come from pgp_dense_grad_term against the S the fit left; the mean gradients are -u' dm_h."""
+        mu, s2, lp, u = np.empty(n), np.empty(n), np.empty(n), np.empty(n)
+        nlz2 = np.zeros(2)
+        _lib.check(lib.pgp_loo_fit_dense(ctx, _lib.ptr(K), n, _lib.ptr(r), log_sn, want, _lib.ptr(alpha), _lib.ptr(mu), _lib.ptr(s2),
+                                         _lib.ptr(lp), _lib.ptr(nlz2), _lib.ptr(glik), _lib.ptr(u), C.byref(fh)), "pgp_loo_fit_dense")
+        nlZ[0] = nlz2[0]
+        self._keep(n, mu + m, s2, lp, nlz2, want)
+        return u
+
+    def _call_program(self, ctx, kind, hyp, nc, para, flags, log_sn, m, dm, nm, want, n, alpha, nlZ, g, fh):
+        mu, s2, lp = np.empty(n), np.empty(n), np.empty(n)
+        nlz2 = np.zeros(2)
+        rc = _lib.load().pgp_loo_fit(ctx, kind, _lib.ptr(hyp), nc, int(para), int(flags), log_sn, _lib.ptr(m), _lib.ptr(dm), nm, want,
+                                     _lib.ptr(alpha), _lib.ptr(mu), _lib.ptr(s2), _lib.ptr(lp), _lib.ptr(nlz2), _lib.ptr(g),
+                                     C.byref(fh))
+        _lib.check(rc, "pgp_loo_fit")
+        nlZ[0] = nlz2[0]
+        self._keep(n, mu, s2, lp, nlz2, want)
+
+    def evaluate(self, meanfunc, covfunc, likfunc, x, y, nargout=1):
+        if self.sharded and isinstance(likfunc, _lik.Gauss):
+            raise NotImplementedError("pygps_amd: leave-one-out inference runs on one GPU (the distributed strips of B^-1 of a "
+                                      "sharded fit are out of scope)")
+        return super(LOO, self).evaluate(meanfunc, covfunc, likfunc, x, y, nargout)
 
 
 class EP(Inference):

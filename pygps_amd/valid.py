@@ -81,6 +81,16 @@ _METRICS = {
 }
 
 
+def loo_validation(model, metrics=("RMSE", "NLPD")):
+    """Leave-one-out validation of a fitted-or-not GPR ``model`` on its own data: the n-fold limit of the K-fold loop without
+    a single refit (GPR.predict_loo: closed form from one factorisation, hyper-parameters as they stand).  Returns
+    {metric: value} for the metrics k-fold reports (RMSE, NLPD).  Exact or LOO inference with lik.Gauss only; EP / Laplace
+    cavity LOO, FITC and sharded fits are out of scope."""
+    ymu, ys2, fmu, fs2, lp = model.predict_loo()
+    yt = np.asarray(model.y, dtype=float).reshape(-1, 1)
+    return {name: float(_METRICS[name](ymu, ys2, yt)) for name in metrics}
+
+
 def _one_fold(make_model, x, y, K, k, metrics, numIterations, set_data):
     idx = np.arange(x.shape[0])
     test = idx % K == k
