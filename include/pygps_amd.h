@@ -364,6 +364,22 @@ int pgp_fitc_ep_fit_lik(pgp_ctx* ctx, int kind, const double* covhyp, int ncov, 
                         int want, int warm, double* ttau_io, double* tnu_io, double* alpha_out, double* L_out, double* nlZ_out,
                         double* dnlZ_out, int* sweeps_out, pgp_fitc** handle_out);
 
+/* ---- learned inducing inputs: the FITC fits with the gradient w.r.t. xu ------------------------------------------------------
+ * pgp_fitc_fit / pgp_fitc_ep_fit_lik with one more output: dxu_out (nu, d) row-major like xu, d nlZ / d xu (NULL: exactly the
+ * plain entry points, which forward here).  Written with want = 3 and dnlZ_out set; every other output is bit-identical to a call
+ * without it.  One adjoint matrix serves all nu d coordinates: two more nu x n x nu GEMMs and one fused contraction (csrc/fitc_xu.hip).
+ * Kernels that are a function k(s) of one scaled squared distance: RBF, RBFunit, RBFard, RQ, RQard, Matern d = 3, 5, 7.  Any other
+ * kind (programs, Matern d = 1, PiecePoly, Periodic, Gabor, Const, Noise, SM, ...) with dxu_out set returns
+ * PGP_ERR_XU_UNSUPPORTED before any device work. */
+#define PGP_ERR_XU_UNSUPPORTED (-92)
+int pgp_fitc_fit_xu(pgp_ctx* ctx, int kind, const double* covhyp, int ncov, int para, int flags, double log_sn,
+                    const double* xu, int64_t nu, const double* mvec, const double* dm, int nmean, int want,
+                    double* alpha_out, double* L_out, double* nlZ_out, double* dnlZ_out, pgp_fitc** handle_out, double* dxu_out);
+int pgp_fitc_ep_fit_lik_xu(pgp_ctx* ctx, int kind, const double* covhyp, int ncov, int para, int flags, int lik, const double* likhyp,
+                           int nlik, int ref_compat, const double* xu, int64_t nu, const double* mvec, const double* dm, int nmean,
+                           int want, int warm, double* ttau_io, double* tnu_io, double* alpha_out, double* L_out, double* nlZ_out,
+                           double* dnlZ_out, int* sweeps_out, pgp_fitc** handle_out, double* dxu_out);
+
 /* ---- ONE fit over the GPUs of a node (no reference counterpart: Core/inf.py:353-384 runs on one host) ---
  * One process per GPU, every rank calls with the same data (pgp_set_data) and arguments.  The factorisation is 1-D
  * block-cyclic over column panels; panels are broadcast over `comm`, alpha / nlZ / dnlZ come back identical on every

@@ -27,6 +27,7 @@ MODE_TRAIN, MODE_CROSS, MODE_SELF_TEST = 0, 1, 2
 LIK_ERF, LIK_GAUSS, LIK_LAPLACE = 0, 1, 2
 ERR_LAPLACE_WNEG = -90
 ERR_PROP_NONFINITE = -91
+ERR_XU_UNSUPPORTED = -92           # the gradient w.r.t. the inducing inputs is not built for this kernel
 PROP_NONE, PROP_T, PROP_SPREAD = 0, 1, 2
 PROP_MAX_LABELS = 256             # label classes of pgp_propagation_kernel (include/pygps_amd.h)
 PROP_SORT_LDS = 2048              # keys of one graph sorted on chip; PROP_GRAM_LDS (key, count) pairs of a tile of 32 graphs held on chip
@@ -98,6 +99,11 @@ SIGNATURES = {
     "pgp_fitc_ep_fit_lik": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _dp, _i64,
                                       _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int),
                                       C.POINTER(_vp)]),
+    "pgp_fitc_fit_xu": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _i64, _dp, _dp, C.c_int,
+                                  C.c_int, _dp, _dp, _dp, _dp, C.POINTER(_vp), _dp]),
+    "pgp_fitc_ep_fit_lik_xu": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _dp, _i64,
+                                         _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int),
+                                         C.POINTER(_vp), _dp]),
     "pgp_potrf": (C.c_int, [_vp, _dp, _i64, _dp]),
     "pgp_potrs": (C.c_int, [_vp, _dp, _i64, _dp, _i64, _dp]),
     "pgp_last_timings": (C.c_int, [_vp, _dp]),
@@ -158,6 +164,7 @@ TEST_SIGNATURES = {
     "pgp_test_joint_vpad": (C.c_int, [_vp, _vp, _dp, _i64, C.POINTER(C.c_int), C.POINTER(_i64)]),
     "pgp_test_pool_state": (C.c_int, [_vp, _vp, C.POINTER(_i64)]),
     "pgp_test_read_binv": (C.c_int, [_vp, _i64, _dp]),
+    "pgp_test_fitc_xu_contract": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_int, C.c_int, _i64, _dp, _i64, _dp, _i64, _dp, _dp]),
 }
 
 _lock = threading.RLock()

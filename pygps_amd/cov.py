@@ -828,7 +828,14 @@ class ScaleOfKernel(_Composite):
 class FITCOfKernel(Kernel):
     """Covariance "function" of the FITC approximation (Core/cov.py:332-390): instead of a full matrix it returns the
     (cross-)covariances with the inducing inputs xu -- 'train': (diag K, Kuu, Ku), 'cross': k(xu, z), 'self_test':
-    k(z, z).  inf.FITC_Exact does not call these (the whole fit is one device call); they exist for API parity."""
+    k(z, z).  inf.FITC_Exact does not call these (the whole fit is one device call); they exist for API parity.
+
+    ``learn_inducing`` (GP_FITC.learnInducing): the FITC fits also return d nlZ / d inducingInput as ``dnlZ.xu`` and the optimiser
+    moves the inducing inputs with the hyper-parameters (no reference counterpart; GPML's hyp.xu)."""
+
+    learn_inducing = False
+    #: kernels that are a function of one scaled squared distance with a derivative on the device (csrc/sqdist_tile.h cov_dvalue_ds)
+    _XU_KINDS = (_lib.COV_RBF, _lib.COV_RBFARD, _lib.COV_RBFUNIT, _lib.COV_RQ, _lib.COV_RQARD, _lib.COV_MATERN)
 
     def __init__(self, cov, inducingInput):
         refuse_pre(cov, "the FITC approximation (fitc(u) of a precomputed matrix has no meaning)")
@@ -836,6 +843,17 @@ class FITCOfKernel(Kernel):
         self.inducingInput = np.asarray(inducingInput, dtype=float)
         self.covfunc = cov
         self.para = []
+
+    def _check_learn_inducing(self):
+        """Raise unless the gradient w.r.t. the inducing inputs is built for the wrapped kernel (host check, no device work)."""
+        k = self.covfunc
+        ok = isinstance(k, Kernel) and not isinstance(k, _Composite) and getattr(k, "_kind", None) in self._XU_KINDS
+        if ok and k._kind == _lib.COV_MATERN and k._d() == 1:
+            ok = False
+        if not ok:
+            name = type(k).__name__ + (" with d = 1" if isinstance(k, Matern) else "")
+            raise NotImplementedError("pygps_amd: learning the inducing inputs is not built for %s (RBF, RBFunit, RBFard, RQ, RQard "
+                                      "and Matern d = 3, 5, 7 only; there is no CPU fallback)" % name)
 
     @property
     def hyp(self):

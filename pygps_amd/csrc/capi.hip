@@ -62,6 +62,7 @@ const char* pgp_strerror(int status) {
     if (status == 0) return "ok";
     if (status > 0) return "kernel matrix not positive definite";
     if (status <= PGP_ERR_HIP) return g_err[0] ? g_err : "HIP runtime failure";
+    if (status == PGP_ERR_XU_UNSUPPORTED) return "the gradient w.r.t. the inducing inputs is not built for this covariance function";
     return "bad argument";
 }
 

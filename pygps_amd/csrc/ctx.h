@@ -526,3 +526,21 @@ int laplace_fit_gathered(pgp_ctx* c, const GatherSrc& g, double* nlZ_out, int* s
 // the device core of pgp_predict_dense on a block that is already on the device: Ks (f->np x nrhs, one column per test point,
 // zero padding; overwritten), msd (nb) prior mean; o1 = fmu, o2 = colsum((R'^-1 (sW o Ks))^2)  (fs2 = max(kss - o2, 0))
 int predict_dense_block(pgp_ctx* c, pgp_factor* f, double* Ks, long nb, int nrhs, const double* msd, double* o1, double* o2);
+
+// ---- gradients w.r.t. the FITC inducing inputs (fitc_xu.hip) -------------------------------------------------------------------
+// fitc.hip's split-K GEMM wrapper (C = alpha op(A) op(B)' + beta C, every dimension a multiple of 128)
+int fitc_gemm(pgp_ctx* c, const double* A, long lda, int a_kc, const double* B, long ldb, int b_kc, double* C, long ldc, long M, long N,
+              long K, double alpha, double beta);
+// kinds whose value is a function k(s) of one scaled squared distance with cov_dvalue_ds: no programs, Matern d = 1, PiecePoly, ...
+bool fitc_xu_supported(int kind, int para);
+// doubles of the contraction's partial sums for row points with leading dimension ldr against ncols column points
+long fitc_xu_partial_doubles(long ldr, long ncols, int dpad);
+// out[j, k] = (prev ? prev[j, k] : 0) + 2 scale_k sum_i A(j, i) k'(s_ji) (r_jk - c_ik): row points XrT (dpad x ldr, nr live), column
+// points XcT (dpad x ldc, ncols live), both scaled; A column-major with leading dimension lda; out, prev (nr x d) row-major, device
+int fitc_xu_contract_launch(const double* XrT, long ldr, long nr, const double* XcT, long ldc, long ncols, int d, int dpad,
+                            const CovSpec& cs, const double* A, long lda, const double* scale_dev, double* part, const double* prev,
+                            double* out, hipStream_t st);
+// dnlZ / dxu (nu x d, row-major, host) from the quantities of the FITC gradient pass; R (nup x np), Cm, Sm (nup x nup) are scratch
+int fitc_xu_grad(pgp_ctx* c, const CovSpec& cs, long nu, long nup, const double* XuT, const double* Bm, const double* W,
+                 const double* BW, const double* al_d, const double* cw_d, const double* w_d, double* R, double* Cm, double* Sm,
+                 double* dxu_out);

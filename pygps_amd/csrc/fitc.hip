@@ -207,11 +207,18 @@ int factor_with_inverse(pgp_ctx* c, double* F, long ld, long nup, double* pack) 
 
 }  // namespace
 
+int fitc_gemm(pgp_ctx* c, const double* A, long lda, int a_kc, const double* B, long ldb, int b_kc, double* C, long ldc, long M, long N,
+              long K, double alpha, double beta) {
+    return gemm(c, A, lda, a_kc, B, ldb, b_kc, C, ldc, M, N, K, alpha, beta);
+}
+
 extern "C" {
 
-int pgp_fitc_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para, int flags, double log_sn,
-                 const double* xu, int64_t nu, const double* mvec, const double* dm, int nmean, int want,
-                 double* alpha_out, double* L_out, double* nlZ_out, double* dnlZ_out, pgp_fitc** handle_out) {
+// dxu_out (nu x d, optional): d nlZ / d xu (fitc_xu.hip); null leaves the call exactly what it was without it
+static int fitc_fit_core(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para, int flags, double log_sn,
+                         const double* xu, int64_t nu, const double* mvec, const double* dm, int nmean, int want,
+                         double* alpha_out, double* L_out, double* nlZ_out, double* dnlZ_out, pgp_fitc** handle_out,
+                         double* dxu_out) {
     if (!c) return -1;
     GateShared device_gate_hold(c);
     if (!c) return -1;
@@ -219,6 +226,7 @@ int pgp_fitc_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para,
     if (!covhyp) return -3;
     if (!xu || nu <= 0) return -8;
     if (want < 1 || want > 3) return -11;
+    if (dxu_out && !fitc_xu_supported(kind, para)) return PGP_ERR_XU_UNSUPPORTED;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->st;
     const long n = c->n, d = c->d, np = c->np;
@@ -368,6 +376,8 @@ int pgp_fitc_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para,
             for (long j = 0; j < n; ++j) { s3 += vcol[j] * al[j] * al[j]; s4 += cw[j] * vcol[j]; }
             dnlZ_out[nmean + h] = 0.5 * (dk0 * sum_ig - wq - s3 - s4 - rwbw);            // inf.py:438-439
         }
+        // the same formula for every coordinate of xu at once: R, RW, dKuu are free by now, cs_d still holds cw
+        if (dxu_out) CHK(fitc_xu_grad(c, cs, nu, nup, XuT, Bm, W, BW, al_d, cs_d, w_d, R, RW, dKuu, dxu_out));
         // noise: sn2 part + the snu2 = 1e-6 sn2 part with dKuu = 2 snu2 I, R = -2 snu2 B  (inf.py:441-446)
         double lik = sn2 * (sum_ig - sum_cw - ata);
         lik += 0.5 * (2.0 * snu2 * wtw - 2.0 * snu2 * s_cb_al2 - 2.0 * snu2 * s_cw_cb + 2.0 * snu2 * bwbw);
@@ -393,6 +403,20 @@ int pgp_fitc_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para,
     HIP_TRY(hipStreamSynchronize(st));
     if (c->prof) prof_collect(c);
     return PGP_OK;
+}
+
+int pgp_fitc_fit(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para, int flags, double log_sn,
+                 const double* xu, int64_t nu, const double* mvec, const double* dm, int nmean, int want,
+                 double* alpha_out, double* L_out, double* nlZ_out, double* dnlZ_out, pgp_fitc** handle_out) {
+    return fitc_fit_core(c, kind, covhyp, ncov, para, flags, log_sn, xu, nu, mvec, dm, nmean, want, alpha_out, L_out, nlZ_out, dnlZ_out,
+                         handle_out, nullptr);
+}
+
+int pgp_fitc_fit_xu(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para, int flags, double log_sn,
+                    const double* xu, int64_t nu, const double* mvec, const double* dm, int nmean, int want,
+                    double* alpha_out, double* L_out, double* nlZ_out, double* dnlZ_out, pgp_fitc** handle_out, double* dxu_out) {
+    return fitc_fit_core(c, kind, covhyp, ncov, para, flags, log_sn, xu, nu, mvec, dm, nmean, want, alpha_out, L_out, nlZ_out, dnlZ_out,
+                         handle_out, dxu_out);
 }
 
 // GP.predict with the FITC posterior (Core/gp.py:395-417, dense-L branch :415):  fmu = ms + Ks' alpha,
@@ -597,7 +621,7 @@ extern "C" {
 static int fitc_ep_core(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para, int flags, const double* xu, int64_t nu,
                         const double* mvec, const double* dm, int nmean, int want, int warm, double* ttau_io, double* tnu_io,
                         double* alpha_out, double* L_out, double* nlZ_out, double* dnlZ_out, int* sweeps_out,
-                        pgp_fitc** handle_out, int lik, double log_sn, int ref_compat) {
+                        pgp_fitc** handle_out, int lik, double log_sn, int ref_compat, double* dxu_out = nullptr) {
     if (!c) return -1;
     GateShared device_gate_hold(c);
     if (!c) return -1;
@@ -606,6 +630,7 @@ static int fitc_ep_core(pgp_ctx* c, int kind, const double* covhyp, int ncov, in
     if (!xu || nu <= 0) return -8;
     if (want < 1 || want > 3) return -11;
     if (!ttau_io || !tnu_io) return -12;
+    if (dxu_out && !fitc_xu_supported(kind, para)) return PGP_ERR_XU_UNSUPPORTED;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->st;
     const long n = c->n, d = c->d, np = c->np;
@@ -839,6 +864,8 @@ static int fitc_ep_core(pgp_ctx* c, int kind, const double* covhyp, int ncov, in
             for (long j = 0; j < n; ++j) { s3 += vcol[j] * al[j] * al[j]; s4 += cw[j] * vcol[j]; }
             dnlZ_out[nmean + h] = 0.5 * (dk0 * sum_s - wq - s3 - s4 - rwbw);             // inf.py:917-923
         }
+        // every coordinate of xu at once, at the final sites (1 / g -> s sits in W and al): cs_d still holds cw here
+        if (dxu_out) CHK(fitc_xu_grad(c, cs, nu, nup, XuT, Bm, W, BW, al_d, cs_d, wv_d, R, RW, dKuu, dxu_out));
         for (int i = 0; i < nmean; ++i) {                                                // inf.py:937-941, final cavities
             double s = 0.0;
             for (long j = 0; j < n; ++j) {
@@ -901,6 +928,16 @@ int pgp_fitc_ep_fit_lik(pgp_ctx* c, int kind, const double* covhyp, int ncov, in
     else if (lik != PGP_LIK_LAPLACE || nlik != 1 || !likhyp) return -15;
     return fitc_ep_core(c, kind, covhyp, ncov, para, flags, xu, nu, mvec, dm, nmean, want, warm, ttau_io, tnu_io, alpha_out, L_out,
                         nlZ_out, dnlZ_out, sweeps_out, handle_out, lik, lik == PGP_LIK_LAPLACE ? likhyp[0] : 0.0, ref_compat);
+}
+
+int pgp_fitc_ep_fit_lik_xu(pgp_ctx* c, int kind, const double* covhyp, int ncov, int para, int flags, int lik, const double* likhyp,
+                           int nlik, int ref_compat, const double* xu, int64_t nu, const double* mvec, const double* dm, int nmean,
+                           int want, int warm, double* ttau_io, double* tnu_io, double* alpha_out, double* L_out, double* nlZ_out,
+                           double* dnlZ_out, int* sweeps_out, pgp_fitc** handle_out, double* dxu_out) {
+    if (lik == PGP_LIK_ERF) { if (nlik != 0) return -15; }
+    else if (lik != PGP_LIK_LAPLACE || nlik != 1 || !likhyp) return -15;
+    return fitc_ep_core(c, kind, covhyp, ncov, para, flags, xu, nu, mvec, dm, nmean, want, warm, ttau_io, tnu_io, alpha_out, L_out,
+                        nlZ_out, dnlZ_out, sweeps_out, handle_out, lik, lik == PGP_LIK_LAPLACE ? likhyp[0] : 0.0, ref_compat, dxu_out);
 }
 
 }  // extern "C"

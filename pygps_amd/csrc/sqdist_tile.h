@@ -424,6 +424,22 @@ __device__ __forceinline__ double cov_value(const CovParams& p, double s, bool s
     return p.sf2 * exp_nonpos(-0.5 * s);  // RBF / RBFard
 }
 
+// d cov_value(p, s) / ds, the derivative w.r.t. the scaled squared distance itself (the chain rule to a coordinate of a point:
+// fitc_xu.hip).  RBF / RBFunit / RBFard, RQ / RQard, Matern d = 3, 5, 7 -- every one finite at s = 0 and written directly
+// (with t = sqrt(s):  d/ds [f(t) e^-t] = (f'(t) - f(t)) e^-t / (2 t), and f' - f carries the factor t), never as
+// -(dk / dlog ell) / (2 s), which is 0/0 at coincident points.  Where the exponential underflows the result is an exact zero.
+__device__ __forceinline__ double cov_dvalue_ds(const CovParams& p, double s) {
+    if (p.kind == 4 || p.kind == 6)       // RQ, RQard: sf2 (1 + s / 2 alpha)^-alpha
+        return -0.5 * p.sf2 * exp_nonpos((-p.alpha - 1.0) * log(1.0 + 0.5 * s / p.alpha));
+    if (p.kind == 2) {                    // Matern: (f' - f) / (2 t) = -1/2, -(1 + t) / 6, -(3 + 3 t + t^2) / 30
+        const double t = sqrt(s);
+        const double e = exp_nonpos(-t);
+        const double q = p.md == 3 ? 0.5 : (p.md == 5 ? (1.0 + t) / 6.0 : (3.0 + 3.0 * t + t * t) / 30.0);
+        return e > 0.0 ? -p.sf2 * q * e : 0.0;
+    }
+    return -0.5 * p.sf2 * exp_nonpos(-0.5 * s);   // RBF / RBFard / RBFunit (sf2 = 1)
+}
+
 // derivative w.r.t. hyper p.der; dk2 = scaled squared difference in coordinate p.der (ARD only)
 template <bool EXT = false>
 __device__ __forceinline__ double cov_deriv(const CovParams& p, double s, double dk2, bool same = false) {

@@ -74,6 +74,11 @@ int pgp_test_pool_state(pgp_ctx* ctx, pgp_factor* f, int64_t* out9);
    symmetric row-major (n, n) host matrix once the context's streams are idle.  Reads only, launches nothing but the copy.
    -3: n rounded up to 128 is not the workspace's size */
 int pgp_test_read_binv(pgp_ctx* ctx, int64_t n, double* out);
+/* fitc_xu_contract_kernel (csrc/fitc_xu.hip) alone with caller-given weights: out[j, k] = 2 scale_k sum_i A[j, i] k'(s_ji)
+   (rows~[j, k] - cols~[i, k]) for host rows (nr, d), cols (ncols, d; NULL: the rows again) and A (nr, ncols) row-major; out (nr, d).
+   Needs no resident data.  PGP_ERR_XU_UNSUPPORTED for kinds without cov_dvalue_ds */
+int pgp_test_fitc_xu_contract(pgp_ctx* ctx, int kind, const double* hyp, int ncov, int para, int flags, int64_t d, const double* rows,
+                              int64_t nr, const double* cols, int64_t ncols, const double* A, double* out);
 #ifdef __cplusplus
 }
 #endif

@@ -421,6 +421,14 @@ class GP_FITC(GP):
             self.u = np.array(list(itertools.product(*axes)))
             self.covfunc = self.covfunc.fitc(self.u)
 
+    def learnInducing(self, flag=True):
+        """Treat the inducing inputs as parameters: getPosterior also returns dnlZ.xu and optimize() moves them together with the
+        hyper-parameters (Snelson & Ghahramani's pseudo-inputs).  Call after the covariance function is set (setData / setPrior);
+        a later setPrior(kernel=...) builds a new FITC covariance and clears the flag."""
+        if not isinstance(self.covfunc, cov.FITCOfKernel):
+            raise Exception("To learn the inducing points, please call setData() or setPrior(kernel, inducing_points) first!")
+        self.covfunc.learn_inducing = bool(flag)
+
     def setPrior(self, mean=None, kernel=None, inducing_points=None):
         if kernel is not None:
             if inducing_points is not None:

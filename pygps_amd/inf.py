@@ -53,6 +53,7 @@ class dnlZStruct(object):
         self.mean = [0 for _ in range(len(m.hyp))] if m.hyp is not None else []
         self.cov = [0 for _ in range(len(c.hyp))] if c.hyp is not None else []
         self.lik = [0 for _ in range(len(l.hyp))] if l.hyp is not None else []
+        self.xu = None          # (nu, D) d nlZ / d inducing inputs: the FITC fits with FITCOfKernel.learn_inducing
 
     def __str__(self):
         return ("Derivatives of mean, cov and lik functions:\nmean:" + str(self.mean) + "\ncov:" + str(self.cov)
@@ -686,6 +687,8 @@ class FITC_Exact(Inference):
             raise Exception('Only covFITC supported.')
         _cov.refuse_pre(covfunc.covfunc, "the FITC approximation (fitc(u) of a precomputed matrix has no meaning)")
         _cov.refuse_dot(covfunc.covfunc, "the FITC approximation")
+        if covfunc.learn_inducing:
+            covfunc._check_learn_inducing()
         dev = _lib.default_device() if self.device is None else self.device
         kind, para, flags = _device_kernel(covfunc.covfunc, _lib.ctx(dev))
         x = _lib.f64(x)
@@ -694,6 +697,7 @@ class FITC_Exact(Inference):
         if xu.shape[1] != D:
             raise Exception('Dimensionality of inducing inputs must match training inputs')
         nu = xu.shape[0]
+        dxu = np.zeros((nu, D)) if (covfunc.learn_inducing and nargout > 2) else None
         y = _lib.f64(y).reshape(n)
         _Resident.ensure(x, y, dev)
         m, dm, nm = _mean_inputs(meanfunc, x)
@@ -705,9 +709,13 @@ class FITC_Exact(Inference):
         nlZ = np.zeros(1)
         g = np.zeros(nm + nc + 1)
         fh = C.c_void_p()
-        rc = _lib.load().pgp_fitc_fit(_lib.ctx(dev), kind, _lib.ptr(hyp), nc, int(para), int(flags), log_sn, _lib.ptr(xu), nu,
-                                      _lib.ptr(m), _lib.ptr(dm), nm, int(min(max(nargout, 1), 3)), _lib.ptr(alpha),
-                                      _lib.ptr(Lm), _lib.ptr(nlZ), _lib.ptr(g), C.byref(fh))
+        args = (_lib.ctx(dev), kind, _lib.ptr(hyp), nc, int(para), int(flags), log_sn, _lib.ptr(xu), nu,
+                _lib.ptr(m), _lib.ptr(dm), nm, int(min(max(nargout, 1), 3)), _lib.ptr(alpha),
+                _lib.ptr(Lm), _lib.ptr(nlZ), _lib.ptr(g), C.byref(fh))
+        if dxu is None:
+            rc = _lib.load().pgp_fitc_fit(*args)
+        else:
+            rc = _lib.load().pgp_fitc_fit_xu(*(args + (_lib.ptr(dxu),)))
         _lib.check(rc, "pgp_fitc_fit")
         post = postStruct()
         post.alpha = alpha.reshape(nu, 1)
@@ -721,6 +729,7 @@ class FITC_Exact(Inference):
                 dnlZ.mean = [np.float64(v) for v in g[:nm]]
                 dnlZ.cov = [np.float64(v) for v in g[nm:nm + nc]]
                 dnlZ.lik = [np.float64(g[nm + nc])]
+                dnlZ.xu = dxu
                 return post, nlz, dnlZ
             return post, nlz
         return post
@@ -761,6 +770,8 @@ class FITC_EP(Inference):
         else:
             raise NotImplementedError("pygps_amd: FITC_EP runs on the device for lik.Erf and lik.Laplace only (no CPU fallback)")
         nlik = 0 if likhyp is None else 1
+        if covfunc.learn_inducing:
+            covfunc._check_learn_inducing()
         dev = _lib.default_device() if self.device is None else self.device
         kind, para, flags = _device_kernel(covfunc.covfunc, _lib.ctx(dev))
         x = _lib.f64(x)
@@ -769,6 +780,7 @@ class FITC_EP(Inference):
         if xu.shape[1] != D:
             raise Exception('Dimensionality of inducing inputs must match training inputs')
         nu = xu.shape[0]
+        dxu = np.zeros((nu, D)) if (covfunc.learn_inducing and nargout > 2) else None
         y = _lib.f64(y).reshape(n)
         _Resident.ensure(x, y, dev)
         m, dm, nm = _mean_inputs(meanfunc, x)
@@ -789,11 +801,12 @@ class FITC_EP(Inference):
             _lib.check(lib.pgp_set_option(ctx, b"ep_tol_exp", int(self._tol_exp)), "pgp_set_option")
             _lib.check(lib.pgp_set_option(ctx, b"ep_max_sweep", 1000), "pgp_set_option")
         try:
-            rc = lib.pgp_fitc_ep_fit_lik(ctx, kind, _lib.ptr(hyp), nc, int(para), int(flags), lik,
-                                         _lib.ptr(likhyp) if nlik else None, nlik, int(bool(self.reference_compat)),
-                                         _lib.ptr(xu), nu, _lib.ptr(m), _lib.ptr(dm), nm, int(min(max(nargout, 1), 3)),
-                                         int(warm), _lib.ptr(ttau), _lib.ptr(tnu), _lib.ptr(alpha), _lib.ptr(Lm),
-                                         _lib.ptr(nlZ), _lib.ptr(g), C.byref(sweeps), C.byref(fh))
+            args = (ctx, kind, _lib.ptr(hyp), nc, int(para), int(flags), lik,
+                    _lib.ptr(likhyp) if nlik else None, nlik, int(bool(self.reference_compat)),
+                    _lib.ptr(xu), nu, _lib.ptr(m), _lib.ptr(dm), nm, int(min(max(nargout, 1), 3)),
+                    int(warm), _lib.ptr(ttau), _lib.ptr(tnu), _lib.ptr(alpha), _lib.ptr(Lm),
+                    _lib.ptr(nlZ), _lib.ptr(g), C.byref(sweeps), C.byref(fh))
+            rc = lib.pgp_fitc_ep_fit_lik(*args) if dxu is None else lib.pgp_fitc_ep_fit_lik_xu(*(args + (_lib.ptr(dxu),)))
         finally:
             if self._tol_exp is not None:
                 lib.pgp_set_option(ctx, b"ep_tol_exp", 4)
@@ -816,6 +829,7 @@ class FITC_EP(Inference):
                 dnlZ.mean = [np.float64(v) for v in g[:nm]]
                 dnlZ.cov = [np.float64(v) for v in g[nm:nm + nc]]
                 dnlZ.lik = [np.float64(v) for v in g[nm + nc:]]
+                dnlZ.xu = dxu
                 return post, nlz, dnlZ
             return post, nlz
         return post

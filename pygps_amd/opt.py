@@ -27,14 +27,29 @@ class Optimizer(object):
     def findMin(self, x, y, numIters):
         raise NotImplementedError
 
-    # hyper-parameter vector order is the contract: mean | cov | lik   (Core/opt.py:77-89)
+    def _learns_inducing(self):
+        """True when the model's FITC covariance treats its inducing inputs as parameters (GP_FITC.learnInducing)."""
+        return bool(getattr(getattr(self.model, "covfunc", None), "learn_inducing", False))
+
+    # hyper-parameter vector order is the contract: mean | cov | lik   (Core/opt.py:77-89); with learned inducing inputs their
+    # coordinates follow, row-major: mean | cov | lik | xu.ravel()
     def _convert_to_array(self):
         m = self.model
+        if self._learns_inducing():
+            return np.array(list(m.meanfunc.hyp) + list(m.covfunc.hyp) + list(m.likfunc.hyp)
+                            + np.asarray(m.covfunc.inducingInput, dtype=float).ravel().tolist(), dtype=float)
         return np.array(list(m.meanfunc.hyp) + list(m.covfunc.hyp) + list(m.likfunc.hyp), dtype=float)
 
     def _apply_in_objects(self, hypInArray):
         m = self.model
         Lm, Lc = len(m.meanfunc.hyp), len(m.covfunc.hyp)
+        if self._learns_inducing():
+            nh = Lm + Lc + len(m.likfunc.hyp)
+            arr = np.asarray(hypInArray, dtype=float)
+            u = arr[nh:].reshape(np.shape(m.covfunc.inducingInput)).copy()
+            m.covfunc.inducingInput = u                  # the covariance function and the model name the same points
+            m.u = u
+            hypInArray = arr[:nh]
         v = np.asarray(hypInArray).tolist()
         m.meanfunc.hyp = v[:Lm]
         m.covfunc.hyp = v[Lm:Lm + Lc]
@@ -50,6 +65,8 @@ class Optimizer(object):
     def _nlzAnddnlz(self, hypInArray):
         self._apply_in_objects(hypInArray)
         nlZ, dnlZ, post = self.model.getPosterior()
+        if self._learns_inducing():
+            return nlZ, np.array(list(dnlZ.mean) + list(dnlZ.cov) + list(dnlZ.lik) + np.asarray(dnlZ.xu, dtype=float).ravel().tolist())
         return nlZ, np.array(dnlZ.mean + dnlZ.cov + dnlZ.lik)
 
 
@@ -108,6 +125,7 @@ class Minimize(Optimizer):
 
     def findMin(self, x, y, numIters=200):
         hyp = self._convert_to_array()
+        start = hyp.copy()
         first = self._one(hyp, numIters)
         if not first.ok:
             self.errorCounter += 1
@@ -121,10 +139,14 @@ class Minimize(Optimizer):
         if not (cfg.num_restarts or cfg.min_threshold):
             raise Exception("Specify at least one of the stop conditions")
         best = first if first.ok else None
+        # learned inducing inputs: the ranges cover mean | cov | lik only.  A restart redraws those and starts again from the
+        # inducing inputs the model had when findMin began
+        ndraw = len(ranges) if self._learns_inducing() else hyp.shape[0]
         while True:
             self.trailsCounter += 1
-            for i in range(hyp.shape[0]):                                # global numpy RNG, hyp order
+            for i in range(ndraw):                                       # global numpy RNG, hyp order
                 hyp[i] = np.random.uniform(low=ranges[i][0], high=ranges[i][1])
+            hyp[ndraw:] = start[ndraw:]
             r = self._one(hyp, numIters)
             if r.ok and best is not None:
                 if r.f < best.f:
@@ -285,6 +307,8 @@ class ShardedMinimize(Minimize):
             cfg.num_restarts, cfg.min_threshold = saved
 
     def findMin(self, x, y, numIters=200):
+        if self._learns_inducing():
+            raise NotImplementedError("pygps_amd: ShardedMinimize does not learn inducing inputs (use opt.Minimize)")
         cfg = self.searchConfig
         if not cfg or not (cfg.num_restarts or cfg.min_threshold):
             raise Exception("Specify at least one of the stop conditions")       # Core/opt.py:303-304
