@@ -130,9 +130,7 @@ int pgp_init(int device, pgp_ctx** ctx_out) { GateShared device_gate_hold(device
     return PGP_OK;
 }
 
-// One device buffer for everything a fit returns: [scalars (RES_HEAD doubles: log det, z'z, ... gradient sums from
-// slot 8; the pivot status word in slot RES_INFO) | alpha (np)], fetched with ONE copy into pinned host memory.
-constexpr long RES_HEAD = 272, RES_INFO = 264;
+// the result buffer of a fit (layout: ctx.h RES_HEAD / RES_INFO)
 static int alloc_result_buffer(pgp_ctx* c, long np) {
     const size_t bytes = (size_t)(RES_HEAD + np) * sizeof(double);
     if (c->res_dev) (void)hipFree(c->res_dev);
@@ -975,6 +973,63 @@ int pgp_set_data(pgp_ctx* c, const double* x, int64_t n, int64_t d, const double
 
 }  // extern "C"
 
+// ---- the blocks every fit driver shares (ctx.h) -----------------------------------------------------------------------------
+int ensure_partial(pgp_ctx* c, long need) {
+    if (c->partial_cap >= need) return PGP_OK;
+    if (c->partial) (void)hipFree(c->partial);
+    c->partial = nullptr; c->partial_cap = 0;      // a failed realloc must not leave a dangling pointer behind
+    HIP_TRY(hipMalloc((void**)&c->partial, need * sizeof(double)));
+    c->partial_cap = need;
+    return PGP_OK;
+}
+
+int assemble_train_k(pgp_ctx* c, const CovSpec& cp, const double* Kdense, const GatherSrc* gk, long n, long np, double* Kd, hipStream_t st) {
+    if (gk) return gather_sym_launch(*gk, Kd, np, st);                                  // already on the device, gathered
+    if (Kdense) {
+        HIP_TRY(hipMemcpy2DAsync(Kd, np * sizeof(double), Kdense, n * sizeof(double), n * sizeof(double), n, hipMemcpyHostToDevice, st));
+        return PGP_OK;
+    }
+    CHK(upload_scaled(c, c->x_dev, n, c->d, cp.scale, c->XsT, np, c->dpad, c->scale_dev));
+    if (!gram_assembly_applies(c, cp)) return cov_sym_launch(c->XsT, np, n, c->dpad, cp, Kd, st, np);
+    // RBF / RBFard at d >= 32 (cfg 5: d = 32): the Gram form on the matrix cores
+    CHK(hadamard_prepare_launch(c->XsT, np, n, np, c->dpad, cp, c->prep, st, /*force=*/true));
+    return cov_sym_gram_launch(c->XsT, np, n, c->dpad, cp, Kd, np, c->prep, st);
+}
+
+int finish_factor(pgp_ctx* c, long n, long np, long ldf, FactorGuard& fguard, const CovSpec* cs, double kss, double sn2,
+                  const double* alpha, const double* sW, hipMemcpyKind from, pgp_factor** out) {
+    hipStream_t st = c->st;
+    FactorHandleGuard hg(c, new pgp_factor());
+    pgp_factor* f = hg.f;
+    f->n = n; f->np = np; f->ldf = ldf; f->F = fguard.release(); f->dpad = cs ? c->dpad : 0; f->d = cs ? (int)c->d : 0; f->kss = kss;
+    if (cs) f->cs = *cs;
+    f->sn2 = sn2; f->sw = 1.0 / sqrt(sn2); f->Wd = nullptr; f->XsT = nullptr;
+    const bool host = from == hipMemcpyHostToDevice;             // a host alpha has n entries: the padding is zeroed here
+    CHK(spool_take(c, np * sizeof(double), (void**)&f->alpha));
+    if (host) HIP_TRY(hipMemsetAsync(f->alpha, 0, np * sizeof(double), st));
+    HIP_TRY(hipMemcpyAsync(f->alpha, alpha, (host ? n : np) * sizeof(double), from, st));
+    if (sW) {
+        CHK(spool_take(c, np * sizeof(double), (void**)&f->sWv));
+        HIP_TRY(hipMemcpyAsync(f->sWv, sW, np * sizeof(double), from, st));
+    }
+    if (cs) {
+        CHK(spool_take(c, (size_t)c->dpad * np * sizeof(double), (void**)&f->XsT));
+        HIP_TRY(hipMemcpyAsync(f->XsT, c->XsT, (size_t)c->dpad * np * sizeof(double), hipMemcpyDeviceToDevice, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    *out = hg.release();
+    return PGP_OK;
+}
+
+void loo_copy_out(pgp_ctx* c, LooOut* loo, long n, long np, int want) {
+    const double* v = c->loo_host;
+    if (loo->mu) memcpy(loo->mu, v + LOO_MU * np, n * sizeof(double));
+    if (loo->s2) memcpy(loo->s2, v + LOO_S2 * np, n * sizeof(double));
+    if (loo->lp) memcpy(loo->lp, v + LOO_LP * np, n * sizeof(double));
+    if (loo->u && want >= 3) memcpy(loo->u, v + LOO_U * np, n * sizeof(double));
+    loo->nlZ_loo = v[LOO_HOST_VECS * np];
+}
+
 // Exact.evaluate, and with `loo` its leave-one-out variant (loo.hip): the same stages up to B^-1 and alpha, the same posterior;
 // the LOO tail then replaces B^-1 by S = sn2 Q_loo and hands the gradient pass a zero vector for alpha.  nlZ_out receives the
 // marginal likelihood either way (loo->nlZ_loo the LOO objective); dnlZ_out the gradient of the one the call is about.
@@ -1012,12 +1067,7 @@ static int exact_fit_run(pgp_ctx* c, int kind, const double* covhyp, int ncov, i
     double kss = 0.0;
     if (factor_out && !cp.has_dot()) CHK(cov_point_value(c, cp, 2, &kss));      // (dot-product leaves: predict takes k(z,z) per point)
     const long need = std::max(hadamard_partial_count(np, ncov), 32L * np);       // also the partials of upper_matvec
-    if ((want >= 3 || fused || loo) && c->partial_cap < need) {
-        if (c->partial) (void)hipFree(c->partial);
-        c->partial = nullptr; c->partial_cap = 0;      // a failed realloc must not leave a dangling pointer behind
-        HIP_TRY(hipMalloc((void**)&c->partial, need * sizeof(double)));
-        c->partial_cap = need;
-    }
+    if (want >= 3 || fused || loo) CHK(ensure_partial(c, need));
     const double sn2 = exp(2.0 * log_sn);
     double* F = nullptr;
     CHK(alloc_factor_buffer(c, np, ldf, &F));
@@ -1134,14 +1184,7 @@ static int exact_fit_run(pgp_ctx* c, int kind, const double* covhyp, int ncov, i
         const double logdet = sc_host[0], ztz = sc_host[1];
         *nlZ_out = 0.5 * ztz / sn2 + logdet + 0.5 * (double)n * log(2.0 * M_PI * sn2);
     }
-    if (lbuf) {
-        const double* v = c->loo_host;
-        if (loo->mu) memcpy(loo->mu, v + LOO_MU * np, n * sizeof(double));
-        if (loo->s2) memcpy(loo->s2, v + LOO_S2 * np, n * sizeof(double));
-        if (loo->lp) memcpy(loo->lp, v + LOO_LP * np, n * sizeof(double));
-        if (loo->u && want >= 3) memcpy(loo->u, v + LOO_U * np, n * sizeof(double));
-        loo->nlZ_loo = v[LOO_HOST_VECS * np];
-    }
+    if (lbuf) loo_copy_out(c, loo, n, np, want);
     if (want >= 3 && dnlZ_out) {
         const double* gv = lbuf ? c->loo_host + LOO_U * np : alpha_h;        // LOO: -u' dm_h takes the place of -alpha' dm_h
         for (int i = 0; i < nmean; ++i) {                 // Core/inf.py:378-381
@@ -1153,23 +1196,13 @@ static int exact_fit_run(pgp_ctx* c, int kind, const double* covhyp, int ncov, i
         dnlZ_out[nmean + ncov] = sc_host[8 + ncov];                                     // inf.py:374
     }
     if (factor_out) {
-        FactorHandleGuard hg(c, new pgp_factor());
-        pgp_factor* f = hg.f;
-        f->n = n; f->np = np; f->ldf = ldf; f->F = fguard.release(); f->dpad = c->dpad; f->d = (int)d; f->cs = cp; f->kss = kss;
-        f->sn2 = sn2; f->sw = 1.0 / sqrt(sn2); f->Wd = nullptr;
-        CHK(spool_take(c, np * sizeof(double), (void**)&f->alpha));
-        HIP_TRY(hipMemsetAsync(f->alpha, 0, np * sizeof(double), st));
-        HIP_TRY(hipMemcpyAsync(f->alpha, alpha_h, n * sizeof(double), hipMemcpyHostToDevice, st));
-        CHK(spool_take(c, (size_t)c->dpad * np * sizeof(double), (void**)&f->XsT));
-        HIP_TRY(hipMemcpyAsync(f->XsT, c->XsT, (size_t)c->dpad * np * sizeof(double), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        CHK(finish_factor(c, n, np, ldf, fguard, &cp, kss, sn2, alpha_h, nullptr, hipMemcpyHostToDevice, factor_out));
         // (round 6) the fused inverse rows E = L^-T are what GP.predict's product form needs (W = L^-1 = E'): the handle keeps the
         // scratch buffer instead of the pool, the first predict transposes it (predict.hip ensure_linv) -- no trtri
         if (fused && E && c->keep_inverse && np <= 16384) {
             const size_t eb = pscr.release(E);
-            if (eb) { f->Eraw = E; f->Eraw_bytes = eb; }
+            if (eb) { (*factor_out)->Eraw = E; (*factor_out)->Eraw_bytes = eb; }
         }
-        *factor_out = hg.release();
     }
     fguard.scrub = false;                             // a finished factor honours the pool contract as it is
     return PGP_OK;

@@ -400,6 +400,26 @@ struct FactorHandleGuard {
     pgp_factor* release() { pgp_factor* p = f; f = nullptr; return p; }
 };
 
+// ---- the blocks every fit driver shares (bodies in capi.hip) ------------------------------------------------------------------
+// One device buffer for everything a fit returns: [scalars (RES_HEAD doubles: log det, z'z, ... gradient sums from
+// slot 8; the pivot status word in slot RES_INFO) | alpha (np)], fetched with ONE copy into pinned host memory.
+constexpr long RES_HEAD = 272, RES_INFO = 264;
+struct GatherSrc;
+struct LooOut;
+// c->partial holds at least `need` doubles afterwards (grow-only; a failed reallocation leaves no dangling pointer behind)
+int ensure_partial(pgp_ctx* c, long need);
+// The training covariance of the EP / Laplace drivers, full symmetric into the zeroed padded buffer Kd (np x np): a principal
+// submatrix gathered on the device (gk), a dense upload (Kdense, n x n host), or the device program cp over the resident x
+int assemble_train_k(pgp_ctx* c, const CovSpec& cp, const double* Kdense, const GatherSrc* gk, long n, long np, double* Kd, hipStream_t st);
+// The posterior handle of a finished fit: takes the factor buffer over from fguard, alpha -- and sW where the fit has one per point;
+// without it sw = 1 / sqrt(sn2) -- from the pool: both from the host (alpha: n, its padding zeroed; sW: np) or both from the device (np
+// each), as `from` says; with cs the scaled coordinates of this fit, without (dense, gathered) none.  ONE synchronisation, then
+// *out owns everything; an early return frees what was taken
+int finish_factor(pgp_ctx* c, long n, long np, long ldf, FactorGuard& fguard, const CovSpec* cs, double kss, double sn2,
+                  const double* alpha, const double* sW, hipMemcpyKind from, pgp_factor** out);
+// what a LOO fit left in c->loo_host, to the caller's vectors (u only at want = 3)
+void loo_copy_out(pgp_ctx* c, LooOut* loo, long n, long np, int want);
+
 void prof_collect(pgp_ctx* c);
 static inline long round_up(long v, long m) { return (v + m - 1) / m * m; }
 int make_spec(pgp_ctx* c, int kind, const double* hyp, int nhyp, int para, int flags, int der, long d, CovSpec& cs);

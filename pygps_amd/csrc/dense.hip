@@ -89,12 +89,7 @@ static int dense_fit_run(pgp_ctx* c, const double* K, int64_t n, const double* r
     const bool fused = want >= 3 || (loo && want >= 2);
     CHK(ensure_workspace(c, np));
     const long need = std::max<long>(32L * np, np);
-    if (c->partial_cap < need) {
-        if (c->partial) (void)hipFree(c->partial);
-        c->partial = nullptr; c->partial_cap = 0;
-        HIP_TRY(hipMalloc((void**)&c->partial, need * sizeof(double)));
-        c->partial_cap = need;
-    }
+    CHK(ensure_partial(c, need));
     const double sn2 = exp(2.0 * log_sn);
     double* F = nullptr;
     CHK(alloc_factor_buffer(c, np, ldf, &F));
@@ -149,7 +144,7 @@ static int dense_fit_run(pgp_ctx* c, const double* K, int64_t n, const double* r
         CHK(trsv_bwd_launch(F, ldf, c->W, np, c->zvec, c->alpha_dev, (int)(np / 128), st));
     }
     if (hipGetLastError() != hipSuccess) return PGP_ERR_HIP;
-    HIP_TRY(hipMemcpyAsync(c->res_host, c->res_dev, (size_t)(272 + n) * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(c->res_host, c->res_dev, (size_t)(RES_HEAD + n) * sizeof(double), hipMemcpyDeviceToHost, st));
     if (lbuf) {
         HIP_TRY(hipMemcpyAsync(c->loo_host, lbuf, (size_t)loo_host_doubles(np) * sizeof(double), hipMemcpyDeviceToHost, st));
         if (want >= 3) HIP_TRY(hipMemsetAsync(c->alpha_dev, 0, np * sizeof(double), st));       // behind the copy that took alpha out
@@ -157,32 +152,15 @@ static int dense_fit_run(pgp_ctx* c, const double* K, int64_t n, const double* r
     HIP_TRY(hipStreamSynchronize(st));
     if (c->prof) prof_collect(c);
     int info = 0;
-    memcpy(&info, c->res_host + 264, sizeof(int));
+    memcpy(&info, c->res_host + RES_INFO, sizeof(int));
     if (info != 0) return info > (int)n ? (int)n : info;
-    double* alpha_h = c->res_host + 272;
+    double* alpha_h = c->res_host + RES_HEAD;
     if (!fused) for (long j = 0; j < n; ++j) alpha_h[j] /= sn2;
     if (alpha_out) memcpy(alpha_out, alpha_h, n * sizeof(double));
     if (want >= 2 && nlZ_out) *nlZ_out = 0.5 * c->res_host[1] / sn2 + c->res_host[0] + 0.5 * (double)n * log(2.0 * M_PI * sn2);
     if (want >= 3 && dnlZ_lik_out) *dnlZ_lik_out = c->res_host[8];
-    if (lbuf) {
-        const double* v = c->loo_host;
-        if (loo->mu) memcpy(loo->mu, v + LOO_MU * np, n * sizeof(double));
-        if (loo->s2) memcpy(loo->s2, v + LOO_S2 * np, n * sizeof(double));
-        if (loo->lp) memcpy(loo->lp, v + LOO_LP * np, n * sizeof(double));
-        if (loo->u && want >= 3) memcpy(loo->u, v + LOO_U * np, n * sizeof(double));
-        loo->nlZ_loo = v[LOO_HOST_VECS * np];
-    }
-    if (factor_out) {
-        FactorHandleGuard hg(c, new pgp_factor());
-        pgp_factor* f = hg.f;
-        f->n = n; f->np = np; f->ldf = ldf; f->F = fguard.release(); f->dpad = 0; f->d = 0; f->kss = 0.0;
-        f->sn2 = sn2; f->sw = 1.0 / sqrt(sn2); f->Wd = nullptr; f->XsT = nullptr;
-        CHK(spool_take(c, np * sizeof(double), (void**)&f->alpha));
-        HIP_TRY(hipMemsetAsync(f->alpha, 0, np * sizeof(double), st));
-        HIP_TRY(hipMemcpyAsync(f->alpha, alpha_h, n * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        *factor_out = hg.release();
-    }
+    if (lbuf) loo_copy_out(c, loo, n, np, want);
+    if (factor_out) CHK(finish_factor(c, n, np, ldf, fguard, nullptr, 0.0, sn2, alpha_h, nullptr, hipMemcpyHostToDevice, factor_out));
     fguard.scrub = false;
     if (want >= 3) { c->dense_ready = true; c->dense_n = n; }
     return PGP_OK;

@@ -1172,7 +1172,6 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
     CovSpec cp;
     if (dense) ncov = 0;
     else { const int rc = make_spec(c, kind, covhyp, ncov, para, flags, -1, d, cp); if (rc != PGP_OK) return rc == -11 ? -10 : rc; }
-    const std::vector<double>& sc = cp.scale;
     CHK(ensure_workspace(c, np));
     double kdiag = 0.0;                               // K_ii, identical for every training point (stationary kernels)
     double kss = 0.0;
@@ -1183,12 +1182,7 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
         CHK(cov_point_value(c, cp, 2, &kss));
     }
     const long need = std::max<long>(hadamard_partial_count(np, ncov), np);
-    if (want >= 3 && c->partial_cap < need) {
-        if (c->partial) (void)hipFree(c->partial);
-        c->partial = nullptr; c->partial_cap = 0;      // a failed realloc must not leave a dangling pointer behind
-        HIP_TRY(hipMalloc((void**)&c->partial, need * sizeof(double)));
-        c->partial_cap = need;
-    }
+    if (want >= 3) CHK(ensure_partial(c, need));
     static const bool ep_timing = getenv("PGP_EP_TIMING") != nullptr;      // host wall-clock stamps of the phases (stderr)
     const auto tp0 = std::chrono::steady_clock::now();
     // phase times of this fit, host wall clock (every phase ends synchronised): pgp_last_timings reports them as
@@ -1234,16 +1228,7 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
     FactorGuard fguard(c, w.F, (size_t)ldf * np * sizeof(double), /*scrub=*/true);
     stamp("scratch acquired");
     // ---- K (full symmetric, padded with zeros) --------------------------------------------------------
-    if (gk) EP_TRY(gather_sym_launch(*gk, w.Kd, np, st));                               // already on the device, gathered
-    else if (dense) HIP_TRY(hipMemcpy2DAsync(w.Kd, np * sizeof(double), Kdense, n * sizeof(double), n * sizeof(double), n, hipMemcpyHostToDevice, st));
-    else {
-        EP_TRY(upload_scaled(c, c->x_dev, n, d, sc, c->XsT, np, c->dpad, c->scale_dev));
-        if (gram_assembly_applies(c, cp)) {            // RBF / RBFard at d >= 32 (cfg 5: d = 32): the Gram form on the matrix cores
-            EP_TRY(hadamard_prepare_launch(c->XsT, np, n, np, c->dpad, cp, c->prep, st, /*force=*/true));
-            EP_TRY(cov_sym_gram_launch(c->XsT, np, n, c->dpad, cp, w.Kd, np, c->prep, st));
-        } else
-        EP_TRY(cov_sym_launch(c->XsT, np, n, c->dpad, cp, w.Kd, st, np));
-    }
+    EP_TRY(assemble_train_k(c, cp, Kdense, gk, n, np, w.Kd, st));
     std::vector<double> m(n, 0.0), y(n), ttau(n, 0.0), tnu(n, 0.0), mu(n, 0.0), dsig(n, kdiag);
     if (mvec) memcpy(m.data(), mvec, n * sizeof(double));
     HIP_TRY(hipMemcpyAsync(y.data(), y_dev, n * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1595,22 +1580,7 @@ static int ep_fit_core(pgp_ctx* c, const double* Kdense, int kind, const double*
     c->last_ms[PGP_STAGE_GRAD] = ph_ms[3]; c->last_ms[PGP_STAGE_TRTRI] = 0.0; c->last_ms[PGP_STAGE_LAUUM] = 0.0;
     c->last_ms[PGP_STAGE_TOTAL] = ph_ms[0] + ph_ms[1] + ph_ms[2] + ph_ms[3];
     if (factor_out) {
-        FactorHandleGuard hg(c, new pgp_factor());
-        pgp_factor* f = hg.f;
-        f->n = n; f->np = np; f->ldf = ldf; f->F = fguard.release(); f->dpad = dense ? 0 : c->dpad; f->d = dense ? 0 : (int)d; f->kss = kss;
-        if (!dense) f->cs = cp;
-        f->sn2 = 1.0; f->sw = 1.0; f->Wd = nullptr; f->XsT = nullptr;
-        CHK(spool_take(c, np * sizeof(double), (void**)&f->alpha));
-        HIP_TRY(hipMemsetAsync(f->alpha, 0, np * sizeof(double), st));
-        HIP_TRY(hipMemcpyAsync(f->alpha, alpha.data(), n * sizeof(double), hipMemcpyHostToDevice, st));
-        CHK(spool_take(c, np * sizeof(double), (void**)&f->sWv));
-        HIP_TRY(hipMemcpyAsync(f->sWv, sW.data(), np * sizeof(double), hipMemcpyHostToDevice, st));
-        if (!dense) {
-            CHK(spool_take(c, (size_t)c->dpad * np * sizeof(double), (void**)&f->XsT));
-            HIP_TRY(hipMemcpyAsync(f->XsT, c->XsT, (size_t)c->dpad * np * sizeof(double), hipMemcpyDeviceToDevice, st));
-        }
-        HIP_TRY(hipStreamSynchronize(st));
-        *factor_out = hg.release();
+        CHK(finish_factor(c, n, np, ldf, fguard, dense ? nullptr : &cp, kss, 1.0, alpha.data(), sW.data(), hipMemcpyHostToDevice, factor_out));
     } else {
         HIP_TRY(hipStreamSynchronize(st));
         fguard.scrub = false;                         // a finished factor honours the pool contract (zeros above the diagonal)

@@ -205,6 +205,63 @@ int factor_with_inverse(pgp_ctx* c, double* F, long ld, long nup, double* pack) 
     return rc;
 }
 
+// The head both FITC fits share (inf.py:409-415, 835-848): inducing coordinates up, Ku, Kuu / snu2 + I = L'L' with E1 = L'^-T
+// (upper; Luu^-1 = E1 / sqrt(snu2)) in F1, V = Luu'^-1 Ku and the column sums of V o V, read back with y and the prior mean.
+// xud, XuT, Ku, F1 (zeroed), pack, V, cs_d are the caller's scratch; a pivot that fails returns min(its index, nu)
+struct FitcHead { double* E1 = nullptr; std::vector<double> csum, yh, mh; };
+int fitc_head(pgp_ctx* c, const CovSpec& cs, const double* xu, long nu, long nup, double snu2, const double* mvec, double* xud,
+              double* XuT, double* Ku, double* F1, double* pack, double* V, double* cs_d, FitcHead& h) {
+    hipStream_t st = c->st;
+    const long n = c->n, d = c->d, np = c->np, ldf = 2 * nup + 128;
+    const int dpad = c->dpad;
+    HIP_TRY(hipMemcpyAsync(xud, xu, (size_t)nu * d * sizeof(double), hipMemcpyHostToDevice, st));
+    CHK(upload_scaled(c, c->x_dev, n, d, cs.scale, c->XsT, np, dpad, c->scale_dev));
+    CHK(scale_transpose_launch(xud, nu, (int)d, c->scale_dev, XuT, nup, dpad, st));
+    // Ku (nup x np, column-major, ld nup) = row-major (n x nu) view of the tile kernel: rows = data, columns = inducing
+    CHK(cov_rect_launch(c->XsT, np, n, XuT, nup, nu, dpad, cs, Ku, nup, st));
+    CHK(cov_factor_launch(XuT, nup, nu, nup, dpad, cs, 1.0 / snu2, F1, ldf, st));       // Kuu / snu2 + I (inf.py:412)
+    CHK(factor_with_inverse(c, F1, ldf, nup, pack));
+    h.E1 = F1 + nup + 128;
+    int info = 0;
+    HIP_TRY(hipMemcpyAsync(&info, c->info_dev, sizeof(int), hipMemcpyDeviceToHost, st));
+    CHK(gemm(c, h.E1, ldf, 1, Ku, nup, 1, V, nup, nup, np, nup, 1.0 / sqrt(snu2), 0.0)); // V = Luu'^-1 Ku
+    CHK(colsumsq(V, nup, nup, np, cs_d, st));
+    h.csum.resize(n); h.yh.resize(n); h.mh.assign(n, 0.0);
+    HIP_TRY(hipMemcpyAsync(h.csum.data(), cs_d, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h.yh.data(), c->y_dev, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (info != 0) return info > (int)nu ? (int)nu : info;
+    if (mvec) memcpy(h.mh.data(), mvec, n * sizeof(double));
+    return PGP_OK;
+}
+
+// A FITC handle under construction: freed (with every buffer it took) on an early return.
+struct FitcHandleGuard {
+    pgp_ctx* c; pgp_fitc* f;
+    ~FitcHandleGuard() { if (f) pgp_fitc_free(c, f); }
+    pgp_fitc* release() { pgp_fitc* p = f; f = nullptr; return p; }
+};
+
+// The posterior handle of a finished FITC fit: copies of the scaled inducing coordinates, alpha (nup) and post.L (nup x nup), pooled
+// (hipFree would synchronise the device); ONE synchronisation, then *out owns them
+int finish_fitc(pgp_ctx* c, long nu, long nup, const CovSpec& cs, double kss, const double* XuT, const double* alpha_d, const double* Lp,
+                pgp_fitc** out) {
+    hipStream_t st = c->st;
+    const size_t xb = (size_t)c->dpad * nup * sizeof(double), sq = (size_t)nup * nup * sizeof(double);
+    FitcHandleGuard hg{c, new pgp_fitc()};
+    pgp_fitc* f = hg.f;
+    f->nu = nu; f->nup = nup; f->d = (int)c->d; f->dpad = c->dpad; f->cs = cs; f->kss = kss;
+    CHK(spool_take(c, xb, (void**)&f->XuT));
+    CHK(spool_take(c, nup * sizeof(double), (void**)&f->alpha));
+    CHK(spool_take(c, sq, (void**)&f->Lpost));
+    HIP_TRY(hipMemcpyAsync(f->XuT, XuT, xb, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(f->alpha, alpha_d, nup * sizeof(double), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(f->Lpost, Lp, sq, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *out = hg.release();
+    return PGP_OK;
+}
+
 }  // namespace
 
 int fitc_gemm(pgp_ctx* c, const double* A, long lda, int a_kc, const double* B, long ldb, int b_kc, double* C, long ldc, long M, long N,
@@ -262,26 +319,12 @@ static int fitc_fit_core(pgp_ctx* c, int kind, const double* covhyp, int ncov, i
     HIP_TRY(hipMemsetAsync(Ku, 0, big, st));
     HIP_TRY(hipMemsetAsync(c->info_dev, 0, sizeof(int), st));
 
-    // ---- coordinates, Ku, Kuu ----------------------------------------------------------------------------
-    HIP_TRY(hipMemcpyAsync(xud, xu, (size_t)nu * d * sizeof(double), hipMemcpyHostToDevice, st));
-    CHK(upload_scaled(c, c->x_dev, n, d, cs.scale, c->XsT, np, dpad, c->scale_dev));
-    CHK(scale_transpose_launch(xud, nu, (int)d, c->scale_dev, XuT, nup, dpad, st));
-    // Ku (nup x np, column-major, ld nup) = row-major (n x nu) view of the tile kernel: rows = data, columns = inducing
-    CHK(cov_rect_launch(c->XsT, np, n, XuT, nup, nu, dpad, cs, Ku, nup, st));
-    CHK(cov_factor_launch(XuT, nup, nu, nup, dpad, cs, 1.0 / snu2, F1, ldf, st));       // Kuu / snu2 + I (inf.py:412)
-    CHK(factor_with_inverse(c, F1, ldf, nup, pack));
-    double* E1 = F1 + nup + 128;                             // L'^-T, upper; Luu^-1 = E1 / sqrt(snu2)
+    // ---- coordinates, Ku, Kuu, V; g ---------------------------------------------------------------------
+    FitcHead head;
+    CHK(fitc_head(c, cs, xu, nu, nup, snu2, mvec, xud, XuT, Ku, F1, pack, V, cs_d, head));
+    double* E1 = head.E1;                                    // L'^-T, upper; Luu^-1 = E1 / sqrt(snu2)
+    const std::vector<double> &csum = head.csum, &yh = head.yh, &mh = head.mh;
     int info = 0;
-    HIP_TRY(hipMemcpyAsync(&info, c->info_dev, sizeof(int), hipMemcpyDeviceToHost, st));
-    // ---- V, g --------------------------------------------------------------------------------------------
-    CHK(gemm(c, E1, ldf, 1, Ku, nup, 1, V, nup, nup, np, nup, isnu, 0.0));               // V = Luu'^-1 Ku
-    CHK(colsumsq(V, nup, nup, np, cs_d, st));
-    std::vector<double> csum(n), yh(n), mh(n, 0.0);
-    HIP_TRY(hipMemcpyAsync(csum.data(), cs_d, n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(yh.data(), c->y_dev, n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (info != 0) return info > (int)nu ? (int)nu : info;
-    if (mvec) memcpy(mh.data(), mvec, n * sizeof(double));
     std::vector<double> g(n), isg(n), r(n);
     double sum_logg = 0.0, rtr = 0.0, sum_ig = 0.0;
     for (long j = 0; j < n; ++j) {
@@ -388,18 +431,7 @@ static int fitc_fit_core(pgp_ctx* c, int kind, const double* covhyp, int ncov, i
             dnlZ_out[i] = -s;
         }
     }
-    if (handle_out) {
-        pgp_fitc* f = new pgp_fitc();
-        f->nu = nu; f->nup = nup; f->d = (int)d; f->dpad = dpad; f->cs = cs; f->kss = kss;
-        CHK(spool_take(c, (size_t)dpad * nup * sizeof(double), (void**)&f->XuT));      // pooled: hipFree would synchronise the device
-        CHK(spool_take(c, nup * sizeof(double), (void**)&f->alpha));
-        CHK(spool_take(c, (size_t)nup * nup * sizeof(double), (void**)&f->Lpost));
-        HIP_TRY(hipMemcpyAsync(f->XuT, XuT, (size_t)dpad * nup * sizeof(double), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(f->alpha, alpha_d, nup * sizeof(double), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(f->Lpost, Lp, sq, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        *handle_out = f;
-    }
+    if (handle_out) CHK(finish_fitc(c, nu, nup, cs, kss, XuT, alpha_d, Lp, handle_out));
     HIP_TRY(hipStreamSynchronize(st));
     if (c->prof) prof_collect(c);
     return PGP_OK;
@@ -677,23 +709,11 @@ static int fitc_ep_core(pgp_ctx* c, int kind, const double* covhyp, int ncov, in
     HIP_TRY(hipMemsetAsync(c->info_dev, 0, sizeof(int), st));
 
     // ---- coordinates, Ku, Kuu, V, d0 (inf.py:835-848) ---------------------------------------------------------
-    HIP_TRY(hipMemcpyAsync(xud, xu, (size_t)nu * d * sizeof(double), hipMemcpyHostToDevice, st));
-    CHK(upload_scaled(c, c->x_dev, n, d, cs.scale, c->XsT, np, dpad, c->scale_dev));
-    CHK(scale_transpose_launch(xud, nu, (int)d, c->scale_dev, XuT, nup, dpad, st));
-    CHK(cov_rect_launch(c->XsT, np, n, XuT, nup, nu, dpad, cs, Ku, nup, st));
-    CHK(cov_factor_launch(XuT, nup, nu, nup, dpad, cs, 1.0 / snu2, F1, ldf, st));       // Kuu / snu2 + I
-    CHK(factor_with_inverse(c, F1, ldf, nup, pack));
-    double* E1 = F1 + nup + 128;
+    FitcHead head;
+    CHK(fitc_head(c, cs, xu, nu, nup, snu2, mvec, xud, XuT, Ku, F1, pack, V, cs_d, head));
+    double* E1 = head.E1;
+    const std::vector<double> &csum = head.csum, &yh = head.yh, &mh = head.mh;
     int info = 0;
-    HIP_TRY(hipMemcpyAsync(&info, c->info_dev, sizeof(int), hipMemcpyDeviceToHost, st));
-    CHK(gemm(c, E1, ldf, 1, Ku, nup, 1, V, nup, nup, np, nup, isnu, 0.0));               // V = Luu'^-1 Ku
-    CHK(colsumsq(V, nup, nup, np, cs_d, st));
-    std::vector<double> csum(n), yh(n), mh(n, 0.0);
-    HIP_TRY(hipMemcpyAsync(csum.data(), cs_d, n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(yh.data(), c->y_dev, n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (info != 0) return info > (int)nu ? (int)nu : info;
-    if (mvec) memcpy(mh.data(), mvec, n * sizeof(double));
     std::vector<double> d0(n), w(n, 0.0), bb(n, 0.0), t(n), sv(n), sqs(n), tb(n), cu(n), vh(n), tau_n(n), nu_n(n);
     for (long j = 0; j < n; ++j) d0[j] = kss - csum[j];                                   // inf.py:848
     HIP_TRY(hipMemcpyAsync(d0_d, d0.data(), n * sizeof(double), hipMemcpyHostToDevice, st));
@@ -895,18 +915,7 @@ static int fitc_ep_core(pgp_ctx* c, int kind, const double* covhyp, int ncov, in
             dnlZ_out[nmean + ncov] = -dh + snu2 * z;
         }
     }
-    if (handle_out) {
-        pgp_fitc* f = new pgp_fitc();
-        f->nu = nu; f->nup = nup; f->d = (int)d; f->dpad = dpad; f->cs = cs; f->kss = kss;
-        CHK(spool_take(c, (size_t)dpad * nup * sizeof(double), (void**)&f->XuT));
-        CHK(spool_take(c, nup * sizeof(double), (void**)&f->alpha));
-        CHK(spool_take(c, (size_t)nup * nup * sizeof(double), (void**)&f->Lpost));
-        HIP_TRY(hipMemcpyAsync(f->XuT, XuT, (size_t)dpad * nup * sizeof(double), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(f->alpha, alpha_d, nup * sizeof(double), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(f->Lpost, Lp, sq, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        *handle_out = f;
-    }
+    if (handle_out) CHK(finish_fitc(c, nu, nup, cs, kss, XuT, alpha_d, Lp, handle_out));
     HIP_TRY(hipStreamSynchronize(st));
     if (c->prof) prof_collect(c);
     return PGP_OK;

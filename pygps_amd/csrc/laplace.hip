@@ -298,12 +298,7 @@ static int laplace_fit_core(pgp_ctx* c, const double* Kdense, int kind, const do
     double kss = 0.0;
     if (!dense && !cp.has_dot()) CHK(cov_point_value(c, cp, 2, &kss));          // only stored for predict (dot-product leaves: per point there)
     const long need = std::max<long>(hadamard_partial_count(np, ncov), np);
-    if (want >= 3 && c->partial_cap < need) {
-        if (c->partial) (void)hipFree(c->partial);
-        c->partial = nullptr; c->partial_cap = 0;
-        HIP_TRY(hipMalloc((void**)&c->partial, need * sizeof(double)));
-        c->partial_cap = need;
-    }
+    if (want >= 3) CHK(ensure_partial(c, need));
     // phase times (host wall clock, every phase ends synchronised) and the factorisations' share of the Newton loop (events)
     double ph_ms[4] = {0.0, 0.0, 0.0, 0.0}, potrf_ms = 0.0;
     auto tlast = std::chrono::steady_clock::now();
@@ -337,16 +332,7 @@ static int laplace_fit_core(pgp_ctx* c, const double* Kdense, int kind, const do
     CHK(alloc_factor_buffer(c, np, ldf, &w.F));
     FactorGuard fguard(c, w.F, (size_t)ldf * np * sizeof(double), /*scrub=*/true);
     // ---- K (full symmetric, padded with zeros) --------------------------------------------------------------------
-    if (gk) CHK(gather_sym_launch(*gk, w.Kd, np, st));                                  // already on the device, gathered
-    else if (dense) HIP_TRY(hipMemcpy2DAsync(w.Kd, np * sizeof(double), Kdense, n * sizeof(double), n * sizeof(double), n, hipMemcpyHostToDevice, st));
-    else {
-        CHK(upload_scaled(c, c->x_dev, n, d, cp.scale, c->XsT, np, c->dpad, c->scale_dev));
-        if (gram_assembly_applies(c, cp)) {
-            CHK(hadamard_prepare_launch(c->XsT, np, n, np, c->dpad, cp, c->prep, st, /*force=*/true));
-            CHK(cov_sym_gram_launch(c->XsT, np, n, c->dpad, cp, w.Kd, np, c->prep, st));
-        } else
-            CHK(cov_sym_launch(c->XsT, np, n, c->dpad, cp, w.Kd, st, np));
-    }
+    CHK(assemble_train_k(c, cp, Kdense, gk, n, np, w.Kd, st));
     if (gk) HIP_TRY(hipMemcpyAsync(w.m, gk->m, n * sizeof(double), hipMemcpyDeviceToDevice, st));       // gathered with K
     else if (mvec) HIP_TRY(hipMemcpyAsync(w.m, mvec, n * sizeof(double), hipMemcpyHostToDevice, st));
     double red[4];
@@ -490,23 +476,8 @@ static int laplace_fit_core(pgp_ctx* c, const double* Kdense, int kind, const do
     c->last_ms[PGP_STAGE_ASSEMBLE] = ph_ms[0]; c->last_ms[PGP_STAGE_SOLVE] = ph_ms[1]; c->last_ms[PGP_STAGE_POTRF] = potrf_ms;
     c->last_ms[PGP_STAGE_GRAD] = ph_ms[2]; c->last_ms[PGP_STAGE_TRTRI] = 0.0; c->last_ms[PGP_STAGE_LAUUM] = 0.0;
     c->last_ms[PGP_STAGE_TOTAL] = ph_ms[0] + ph_ms[1] + ph_ms[2];
-    if (factor_out) {                                 // exactly EP's posterior handle (ep.hip): predict serves it unchanged
-        FactorHandleGuard hg(c, new pgp_factor());
-        pgp_factor* fh = hg.f;
-        fh->n = n; fh->np = np; fh->ldf = ldf; fh->F = fguard.release(); fh->dpad = dense ? 0 : c->dpad; fh->d = dense ? 0 : (int)d;
-        fh->kss = kss;
-        if (!dense) fh->cs = cp;
-        fh->sn2 = 1.0; fh->sw = 1.0; fh->Wd = nullptr; fh->XsT = nullptr;
-        CHK(spool_take(c, np * sizeof(double), (void**)&fh->alpha));
-        HIP_TRY(hipMemcpyAsync(fh->alpha, w.alpha, np * sizeof(double), hipMemcpyDeviceToDevice, st));
-        CHK(spool_take(c, np * sizeof(double), (void**)&fh->sWv));
-        HIP_TRY(hipMemcpyAsync(fh->sWv, w.sW, np * sizeof(double), hipMemcpyDeviceToDevice, st));
-        if (!dense) {
-            CHK(spool_take(c, (size_t)c->dpad * np * sizeof(double), (void**)&fh->XsT));
-            HIP_TRY(hipMemcpyAsync(fh->XsT, c->XsT, (size_t)c->dpad * np * sizeof(double), hipMemcpyDeviceToDevice, st));
-        }
-        HIP_TRY(hipStreamSynchronize(st));
-        *factor_out = hg.release();
+    if (factor_out) {                                 // EP's posterior handle, from the device: predict serves it unchanged
+        CHK(finish_factor(c, n, np, ldf, fguard, dense ? nullptr : &cp, kss, 1.0, w.alpha, w.sW, hipMemcpyDeviceToDevice, factor_out));
     } else {
         HIP_TRY(hipStreamSynchronize(st));
         fguard.scrub = false;                         // a finished factor honours the pool contract (zeros above the diagonal)

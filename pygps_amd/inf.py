@@ -7,6 +7,7 @@ assembly, Cholesky, solves, nlZ and all hyper-gradients -- is ONE call into the 
 hyp, Core/opt.py:70-75); ``post.L`` is a lazy host view of the device-resident factor so that a fit
 is not a PCIe benchmark.  No CPU fallback.
 """
+import contextlib
 import ctypes as C
 import hashlib
 import logging
@@ -240,6 +241,107 @@ def _mean_inputs(meanfunc, x):
     return m, dm, nm
 
 
+class _Inputs(object):
+    """What ``_prepare`` hands an engine: dev, ctx, lib, x (n, D), y (n), m, dm, nm, hyp, dense and -- unless dense -- kind,
+    para, flags of the bound kernel."""
+
+
+def _prepare(device, meanfunc, covfunc, x, y, dense_ok=True, reserve=True, resident=True, inner=False):
+    """The inputs every engine prepares, in the order of their side effects: the cov.Pre check, the kernel bound to the
+    context (``covfunc.covfunc`` with ``inner``: the FITC engines), room for the factor, (x, y) resident on the device.
+    ``dense_ok``: covariance trees that are not device programs take the dense route instead of raising."""
+    p = _Inputs()
+    p.dev = _lib.default_device() if device is None else device
+    kernel = covfunc.covfunc if inner else covfunc
+    _check_pre(kernel, x)                           # (a host check: raises before anything reaches the device)
+    p.dense = dense_ok and _dense_route(kernel)
+    p.lib, p.ctx = _lib.load(), _lib.ctx(p.dev)
+    if not p.dense:
+        p.kind, p.para, p.flags = _device_kernel(kernel, p.ctx)
+    p.x = _lib.f64(x)
+    p.n, p.D = p.x.shape
+    p.y = _lib.f64(y).reshape(p.n)
+    if reserve:
+        DeviceFactor.reserve(p.n, p.dev)
+    if resident:
+        _Resident.ensure(p.x, p.y, p.dev)
+    p.m, p.dm, p.nm = _mean_inputs(meanfunc, p.x)
+    p.hyp = _lib.f64(np.asarray(covfunc.hyp, dtype=float))
+    return p
+
+
+def _want(nargout):
+    return int(min(max(nargout, 1), 3))
+
+
+def _lik_args(likfunc, accepted, refusal):
+    """(lik, likhyp, nlik) of the C entry points for a likelihood among the classes ``accepted``; NotImplementedError(refusal)
+    for any other."""
+    for cls, code in ((_lik.Erf, _lib.LIK_ERF), (_lik.Laplace, _lib.LIK_LAPLACE), (_lik.Gauss, _lib.LIK_GAUSS)):
+        if cls in accepted and isinstance(likfunc, cls):
+            if cls is _lik.Erf:
+                return code, None, 0
+            return code, _lib.f64(np.asarray(likfunc.hyp, dtype=float).reshape(-1)), 1
+    raise NotImplementedError(refusal)
+
+
+_OPTION_DEFAULTS = {b"ep_tol_exp": 4, b"ep_max_sweep": 10, b"laplace_tol_exp": 6}
+
+
+@contextlib.contextmanager
+def _options(lib, ctx, values):
+    """Context options {name: value} for the block; back at the library's defaults on exit, raised or not."""
+    try:
+        for name, v in values.items():
+            _lib.check(lib.pgp_set_option(ctx, name, int(v)), "pgp_set_option")
+        yield
+    finally:
+        for name in values:
+            lib.pgp_set_option(ctx, name, _OPTION_DEFAULTS[name])
+
+
+def _ep_options(tol_exp):
+    """The private sweep tolerance of EP / FITC_EP (gradient checks): with it, as many sweeps as it takes."""
+    return {} if tol_exp is None else {b"ep_tol_exp": tol_exp, b"ep_max_sweep": 1000}
+
+
+def _dense_cov_grads(lib, ctx, covfunc, x, n, log_sn):
+    """The dense route's covariance gradients, one derivative matrix at a time (Core/inf.py:376-377, 536-541, 780-786), against
+    what the dense fit with want = 3 that directly precedes left in the workspace."""
+    g, out = np.zeros(1), []
+    for h in range(len(covfunc.hyp)):
+        dK = _lib.f64(covfunc.getDerMatrix(x=x, mode="train", der=h))
+        _lib.check(lib.pgp_dense_grad_term(ctx, _lib.ptr(dK), n, log_sn, _lib.ptr(g)), "pgp_dense_grad_term")
+        out.append(np.float64(g[0]))
+    return out
+
+
+def _dnlZ(meanfunc, covfunc, likfunc, g, nm, nc, nlik, cov=None):
+    """dnlZStruct from g = [mean (nm) | cov (nc) | lik (nlik) ...]; ``cov`` replaces the middle part (dense route: nc = 0)."""
+    d = dnlZStruct(meanfunc, covfunc, likfunc)
+    d.mean = [np.float64(v) for v in g[:nm]]
+    d.cov = [np.float64(v) for v in g[nm:nm + nc]] if cov is None else cov
+    d.lik = [np.float64(v) for v in g[nm + nc:nm + nc + nlik]]
+    return d
+
+
+def _returns(nargout, post, nlZ, dnlZ, always_nlZ=False):
+    """post | (post, nlZ) | (post, nlZ, dnlZ) by nargout; EP and Laplace return (post, nlZ) at nargout = 1 too (always_nlZ)."""
+    if nargout > 2:
+        return post, nlZ, dnlZ
+    if nargout > 1 or always_nlZ:
+        return post, nlZ
+    return post
+
+
+def _posterior(alpha, sW, L, dense=False):
+    post = postStruct()
+    post.alpha, post.sW, post.L = alpha, sW, L
+    if dense:
+        post.L.dense = True                          # predict hands the cross-covariance block in (GP._latent)
+    return post
+
+
 class Exact(Inference):
     """Exact inference for a Gaussian likelihood (Core/inf.py:345-384)."""
 
@@ -273,63 +375,35 @@ class Exact(Inference):
                           "bcast_max_ms": float(ms6[9]),
                           "bcast_GBs": float(ms6[8]) / max(float(ms6[7]), 1e-9) / 1e6 if ms6[7] > 0 else 0.0,
                           "wait_share": float(ms6[6]) / max(float(ms6[1]), 1e-9) if ms6[1] > 0 else 0.0}
-        post = postStruct()
-        post.alpha = alpha.reshape(n, 1)
-        post.sW = np.ones((n, 1)) / np.sqrt(np.exp(2 * log_sn))
-        post.L = Lh if Lh is not None else _sh.DistributedFactor(n, comm, fh)
-        if nargout > 1:
-            if nargout > 2:
-                dnlZ = dnlZStruct(meanfunc, covfunc, likfunc)
-                dnlZ.mean = [np.float64(v) for v in g[:nm]]
-                dnlZ.cov = [np.float64(v) for v in g[nm:nm + nc]]
-                dnlZ.lik = [np.float64(g[nm + nc])]
-                return post, np.float64(nlz), dnlZ
-            return post, np.float64(nlz)
-        return post
+        post = _posterior(alpha.reshape(n, 1), np.ones((n, 1)) / np.sqrt(np.exp(2 * log_sn)),
+                          Lh if Lh is not None else _sh.DistributedFactor(n, comm, fh))
+        dnlZ = _dnlZ(meanfunc, covfunc, likfunc, g, nm, nc, 1) if nargout > 2 else None
+        return _returns(nargout, post, np.float64(nlz), dnlZ)
 
-    def _evaluate_dense(self, meanfunc, covfunc, likfunc, x, y, nargout):
+    def _evaluate_dense(self, p, meanfunc, covfunc, likfunc, nargout):
         """Covariance functions that are not device programs (a tree with more than two ARD leaves or more than 8 leaves /
         products, Core/cov.py:230-328): K and the derivative matrices come from getCovMatrix / getDerMatrix (the children's
         device-built matrices combined on the host), the factorisation with the fused inverse, alpha, nlZ and every Hadamard
         sum sum(Q o dK_h) / 2 run on the device (csrc/dense.hip).  Costs PCIe traffic (n^2 doubles per matrix), never raises."""
-        dev = _lib.default_device() if self.device is None else self.device
-        ctx = _lib.ctx(dev)
-        lib = _lib.load()
-        x = _lib.f64(x)
-        n = x.shape[0]
-        y = _lib.f64(y).reshape(n)
-        m, dm, nm = _mean_inputs(meanfunc, x)
-        nc = len(covfunc.hyp)
+        n, nm = p.n, p.nm
         log_sn = float(likfunc.hyp[0])
-        K = _lib.f64(covfunc.getCovMatrix(x=x, mode="train"))
-        r = _lib.f64(y - m)
+        K = _lib.f64(covfunc.getCovMatrix(x=p.x, mode="train"))
+        r = _lib.f64(p.y - p.m)
         alpha = np.empty(n)
         nlZ = np.zeros(1)
         glik = np.zeros(1)
         fh = C.c_void_p()
-        DeviceFactor.reserve(n, dev)
-        want = int(min(max(nargout, 1), 3))
-        gvec = self._call_dense(lib, ctx, K, n, r, m, log_sn, want, alpha, nlZ, glik, fh)
+        DeviceFactor.reserve(n, p.dev)
+        gvec = self._call_dense(p.lib, p.ctx, K, n, r, p.m, log_sn, _want(nargout), alpha, nlZ, glik, fh)
         del K
-        post = postStruct()
-        post.alpha = alpha.reshape(n, 1)
-        post.sW = np.ones((n, 1)) / np.sqrt(np.exp(2 * log_sn))
-        post.L = DeviceFactor(fh, n, dev, _lib.current_slot())
-        post.L.dense = True                          # predict hands the cross-covariance block in (GP._latent)
-        if nargout > 1:
-            if nargout > 2:
-                g = np.zeros(1)
-                dnlZ = dnlZStruct(meanfunc, covfunc, likfunc)
-                dnlZ.cov = []
-                for h in range(nc):                                               # Core/inf.py:376-377, one matrix at a time
-                    dK = _lib.f64(covfunc.getDerMatrix(x=x, mode="train", der=h))
-                    _lib.check(lib.pgp_dense_grad_term(ctx, _lib.ptr(dK), n, log_sn, _lib.ptr(g)), "pgp_dense_grad_term")
-                    dnlZ.cov.append(np.float64(g[0]))
-                dnlZ.mean = [np.float64(-(dm[i] @ gvec)) for i in range(nm)]      # Core/inf.py:378-381
-                dnlZ.lik = [np.float64(glik[0])]
-                return post, np.float64(nlZ[0]), dnlZ
-            return post, np.float64(nlZ[0])
-        return post
+        post = _posterior(alpha.reshape(n, 1), np.ones((n, 1)) / np.sqrt(np.exp(2 * log_sn)),
+                          DeviceFactor(fh, n, p.dev, _lib.current_slot()), dense=True)
+        dnlZ = None
+        if nargout > 2:
+            cov = _dense_cov_grads(p.lib, p.ctx, covfunc, p.x, n, log_sn)
+            g = [-(p.dm[i] @ gvec) for i in range(nm)] + [glik[0]]                # Core/inf.py:378-381
+            dnlZ = _dnlZ(meanfunc, covfunc, likfunc, g, nm, 0, 1, cov=cov)
+        return _returns(nargout, post, np.float64(nlZ[0]), dnlZ)
 
     # the two device calls, as hooks: inf.LOO overrides them (and nothing else of evaluate / _evaluate_dense)
     def _call_dense(self, lib, ctx, K, n, r, m, log_sn, want, alpha, nlZ, glik, fh):
@@ -351,45 +425,25 @@ class Exact(Inference):
         if self.sharded:
             _cov.refuse_pre(covfunc, "a sharded fit (the panels of a distributed factor are assembled per rank)")
             _cov.refuse_dot(covfunc, "a sharded fit")
-        _check_pre(covfunc, x)
-        if _dense_route(covfunc):
-            if self.sharded:
+            _check_pre(covfunc, x)
+            if _dense_route(covfunc):
                 raise NotImplementedError("pygps_amd: a sharded fit needs a covariance function that runs as a device program")
-            return self._evaluate_dense(meanfunc, covfunc, likfunc, x, y, nargout)
-        if self.sharded:
             return self._evaluate_sharded(meanfunc, covfunc, likfunc, x, y, nargout)
-        dev = _lib.default_device() if self.device is None else self.device
-        kind, para, flags = _device_kernel(covfunc, _lib.ctx(dev))
-        x = _lib.f64(x)
-        n, D = x.shape
-        y = _lib.f64(y).reshape(n)
-        DeviceFactor.reserve(n, dev)
-        _Resident.ensure(x, y, dev)
-        m, dm, nm = _mean_inputs(meanfunc, x)
-        hyp = _lib.f64(np.asarray(covfunc.hyp, dtype=float))
-        nc = len(hyp)
+        dense = _dense_route(covfunc)       # that route hands r = y - m in and makes room for its factor behind getCovMatrix
+        p = _prepare(self.device, meanfunc, covfunc, x, y, reserve=not dense, resident=not dense)
+        if p.dense:
+            return self._evaluate_dense(p, meanfunc, covfunc, likfunc, nargout)
+        n, nm, nc = p.n, p.nm, len(p.hyp)
         log_sn = float(likfunc.hyp[0])
         alpha = np.empty(n)
         nlZ = np.zeros(1)
         g = np.zeros(nm + nc + 1)
         fh = C.c_void_p()
-        self._call_program(_lib.ctx(dev), kind, hyp, nc, para, flags, log_sn, m, dm, nm, int(min(max(nargout, 1), 3)), n, alpha,
-                           nlZ, g, fh)
-        sn2 = np.exp(2 * log_sn)
-        post = postStruct()
-        post.alpha = alpha.reshape(n, 1)
-        post.sW = np.ones((n, 1)) / np.sqrt(sn2)
-        post.L = DeviceFactor(fh, n, dev, _lib.current_slot())
-        if nargout > 1:
-            nlz = np.float64(nlZ[0])
-            if nargout > 2:
-                dnlZ = dnlZStruct(meanfunc, covfunc, likfunc)
-                dnlZ.mean = [np.float64(v) for v in g[:nm]]
-                dnlZ.cov = [np.float64(v) for v in g[nm:nm + nc]]
-                dnlZ.lik = [np.float64(g[nm + nc])]
-                return post, nlz, dnlZ
-            return post, nlz
-        return post
+        self._call_program(p.ctx, p.kind, p.hyp, nc, p.para, p.flags, log_sn, p.m, p.dm, nm, _want(nargout), n, alpha, nlZ, g, fh)
+        post = _posterior(alpha.reshape(n, 1), np.ones((n, 1)) / np.sqrt(np.exp(2 * log_sn)),
+                          DeviceFactor(fh, n, p.dev, _lib.current_slot()))
+        dnlZ = _dnlZ(meanfunc, covfunc, likfunc, g, nm, nc, 1) if nargout > 2 else None
+        return _returns(nargout, post, np.float64(nlZ[0]), dnlZ)
 
 
 class LOO(Exact):
@@ -467,29 +521,14 @@ class EP(Inference):
         self._tol_exp = None            # private: sweep tolerance 10^-_tol_exp instead of the reference's 1e-4 (gradient checks)
 
     def evaluate(self, meanfunc, covfunc, likfunc, x, y, nargout=1):
-        if isinstance(likfunc, _lik.Laplace):
-            lik, likhyp = _lib.LIK_LAPLACE, _lib.f64(np.asarray(likfunc.hyp, dtype=float).reshape(-1))
-        elif isinstance(likfunc, _lik.Erf):
-            lik, likhyp = _lib.LIK_ERF, None
-        else:
-            raise NotImplementedError("pygps_amd: EP runs on the device for lik.Erf and lik.Laplace only (no CPU fallback)")
-        nlik = 0 if likhyp is None else 1
-        dev = _lib.default_device() if self.device is None else self.device
+        lik, likhyp, nlik = _lik_args(likfunc, (_lik.Laplace, _lik.Erf),
+                                      "pygps_amd: EP runs on the device for lik.Erf and lik.Laplace only (no CPU fallback)")
         # covariance functions that are not device programs (Core/cov.py:230-328 composes anything): K and the derivative
         # matrices come from getCovMatrix / getDerMatrix, the sweeps, the posterior, alpha, nlZ and every Hadamard sum
         # 1/2 sum((sW sW' o B^-1 - alpha alpha') o dK_h) (Core/inf.py:780-786) run on the device
-        _check_pre(covfunc, x)
-        dense = _dense_route(covfunc)
-        if not dense:
-            kind, para, flags = _device_kernel(covfunc, _lib.ctx(dev))
-        x = _lib.f64(x)
-        n, D = x.shape
-        y = _lib.f64(y).reshape(n)
-        DeviceFactor.reserve(n, dev)
-        _Resident.ensure(x, y, dev)
-        m, dm, nm = _mean_inputs(meanfunc, x)
-        hyp = _lib.f64(np.asarray(covfunc.hyp, dtype=float))
-        nc = 0 if dense else len(hyp)
+        p = _prepare(self.device, meanfunc, covfunc, x, y)
+        lib, ctx, n, nm, dense = p.lib, p.ctx, p.n, p.nm, p.dense
+        nc = 0 if dense else len(p.hyp)
         warm = self.last_ttau is not None
         ttau = _lib.f64(self.last_ttau).reshape(n).copy() if warm else np.zeros(n)
         tnu = _lib.f64(self.last_tnu).reshape(n).copy() if warm else np.zeros(n)
@@ -499,29 +538,16 @@ class EP(Inference):
         g = np.zeros(nm + nc + 1)
         sweeps = C.c_int()
         fh = C.c_void_p()
-        want = int(min(max(nargout, 1), 3))
-        lib = _lib.load()
-        ctx = _lib.ctx(dev)
-        compat = int(bool(self.reference_compat))
-        lh = _lib.ptr(likhyp) if nlik else None
-        if self._tol_exp is not None:
-            _lib.check(lib.pgp_set_option(ctx, b"ep_tol_exp", int(self._tol_exp)), "pgp_set_option")
-            _lib.check(lib.pgp_set_option(ctx, b"ep_max_sweep", 1000), "pgp_set_option")
-        try:
+        tail = (lik, _lib.ptr(likhyp), nlik, int(bool(self.reference_compat)), _lib.ptr(p.m), _lib.ptr(p.dm), nm, _want(nargout),
+                int(warm), _lib.ptr(ttau), _lib.ptr(tnu), _lib.ptr(alpha), _lib.ptr(sW), _lib.ptr(nlZ), _lib.ptr(g),
+                C.byref(sweeps), C.byref(fh))
+        with _options(lib, ctx, _ep_options(self._tol_exp)):
             if dense:
-                K = _lib.f64(covfunc.getCovMatrix(x=x, mode="train"))
-                rc = lib.pgp_ep_fit_dense_lik(ctx, _lib.ptr(K), lik, lh, nlik, compat, _lib.ptr(m), _lib.ptr(dm), nm, want,
-                                              int(warm), _lib.ptr(ttau), _lib.ptr(tnu), _lib.ptr(alpha), _lib.ptr(sW),
-                                              _lib.ptr(nlZ), _lib.ptr(g), C.byref(sweeps), C.byref(fh))
+                K = _lib.f64(covfunc.getCovMatrix(x=p.x, mode="train"))
+                rc = lib.pgp_ep_fit_dense_lik(ctx, _lib.ptr(K), *tail)
                 del K
             else:
-                rc = lib.pgp_ep_fit_lik(ctx, kind, _lib.ptr(hyp), nc, int(para), int(flags), lik, lh, nlik, compat, _lib.ptr(m),
-                                        _lib.ptr(dm), nm, want, int(warm), _lib.ptr(ttau), _lib.ptr(tnu), _lib.ptr(alpha),
-                                        _lib.ptr(sW), _lib.ptr(nlZ), _lib.ptr(g), C.byref(sweeps), C.byref(fh))
-        finally:
-            if self._tol_exp is not None:
-                lib.pgp_set_option(ctx, b"ep_tol_exp", 4)
-                lib.pgp_set_option(ctx, b"ep_max_sweep", 10)
+                rc = lib.pgp_ep_fit_lik(ctx, p.kind, _lib.ptr(p.hyp), nc, int(p.para), int(p.flags), *tail)
         if rc == -99:
             raise NotImplementedError("pygps_amd: the device EP path is not built in this version")
         _lib.check(rc, "pgp_ep_fit_dense_lik" if dense else "pgp_ep_fit_lik")
@@ -530,27 +556,12 @@ class EP(Inference):
             logging.getLogger(__name__).warning("maximum number of sweeps reached in function infEP")
         self.last_ttau = ttau.reshape(n, 1)
         self.last_tnu = tnu.reshape(n, 1)
-        post = postStruct()
-        post.alpha = alpha.reshape(n, 1)
-        post.sW = sW.reshape(n, 1)
-        post.L = DeviceFactor(fh, n, dev, _lib.current_slot())
-        if dense:
-            post.L.dense = True                      # predict hands the cross-covariance block in (GP._latent)
+        post = _posterior(alpha.reshape(n, 1), sW.reshape(n, 1), DeviceFactor(fh, n, p.dev, _lib.current_slot()), dense)
+        dnlZ = None
         if nargout > 2:
-            dnlZ = dnlZStruct(meanfunc, covfunc, likfunc)
-            dnlZ.mean = [np.float64(v) for v in g[:nm]]
-            if dense:
-                gh = np.zeros(1)
-                dnlZ.cov = []
-                for h in range(len(hyp)):                                         # one derivative matrix at a time
-                    dK = _lib.f64(covfunc.getDerMatrix(x=x, mode="train", der=h))
-                    _lib.check(lib.pgp_dense_grad_term(ctx, _lib.ptr(dK), n, 0.0, _lib.ptr(gh)), "pgp_dense_grad_term")
-                    dnlZ.cov.append(np.float64(gh[0]))
-            else:
-                dnlZ.cov = [np.float64(v) for v in g[nm:nm + nc]]
-            dnlZ.lik = [np.float64(g[nm + nc])] if nlik else []
-            return post, np.float64(nlZ[0]), dnlZ
-        return post, np.float64(nlZ[0])
+            cov = _dense_cov_grads(lib, ctx, covfunc, p.x, n, 0.0) if dense else None
+            dnlZ = _dnlZ(meanfunc, covfunc, likfunc, g, nm, nc, nlik, cov=cov)
+        return _returns(nargout, post, np.float64(nlZ[0]), dnlZ, always_nlZ=True)
 
 
 class Laplace(Inference):
@@ -569,27 +580,14 @@ class Laplace(Inference):
         self._tol_exp = None            # private: Newton tolerance 10^-_tol_exp instead of the reference's 1e-6 (gradient checks)
 
     def _lik_args(self, likfunc):
-        if isinstance(likfunc, _lik.Erf):
-            return _lib.LIK_ERF, None, 0
-        if isinstance(likfunc, _lik.Gauss):
-            return _lib.LIK_GAUSS, _lib.f64(np.asarray(likfunc.hyp, dtype=float)), 1
-        raise NotImplementedError("pygps_amd: Laplace runs on the device for lik.Erf and lik.Gauss only (no CPU fallback)")
+        return _lik_args(likfunc, (_lik.Erf, _lik.Gauss),
+                         "pygps_amd: Laplace runs on the device for lik.Erf and lik.Gauss only (no CPU fallback)")
 
     def evaluate(self, meanfunc, covfunc, likfunc, x, y, nargout=1):
         lik, likhyp, nlik = self._lik_args(likfunc)
-        dev = _lib.default_device() if self.device is None else self.device
-        _check_pre(covfunc, x)
-        dense = _dense_route(covfunc)
-        if not dense:
-            kind, para, flags = _device_kernel(covfunc, _lib.ctx(dev))
-        x = _lib.f64(x)
-        n, D = x.shape
-        y = _lib.f64(y).reshape(n)
-        DeviceFactor.reserve(n, dev)
-        _Resident.ensure(x, y, dev)
-        m, dm, nm = _mean_inputs(meanfunc, x)
-        hyp = _lib.f64(np.asarray(covfunc.hyp, dtype=float))
-        nc = 0 if dense else len(hyp)
+        p = _prepare(self.device, meanfunc, covfunc, x, y)
+        lib, ctx, n, nm, dense = p.lib, p.ctx, p.n, p.nm, p.dense
+        nc = 0 if dense else len(p.hyp)
         last = None if self.last_alpha is None else np.asarray(self.last_alpha, dtype=float).reshape(-1)
         warm = last is not None and last.shape[0] == n
         alpha = _lib.f64(last).copy() if warm else np.zeros(n)
@@ -599,52 +597,27 @@ class Laplace(Inference):
         steps = C.c_int()
         trace = np.zeros((20, 3))
         fh = C.c_void_p()
-        want = int(min(max(nargout, 1), 3))
-        lib = _lib.load()
-        ctx = _lib.ctx(dev)
-        if self._tol_exp is not None:
-            _lib.check(lib.pgp_set_option(ctx, b"laplace_tol_exp", int(self._tol_exp)), "pgp_set_option")
-        try:
+        tail = (lik, _lib.ptr(likhyp), nlik, _lib.ptr(p.m), _lib.ptr(p.dm), nm, _want(nargout), int(warm), _lib.ptr(alpha),
+                _lib.ptr(sW), _lib.ptr(nlZ), _lib.ptr(g), C.byref(steps), _lib.ptr(trace), C.byref(fh))
+        with _options(lib, ctx, {} if self._tol_exp is None else {b"laplace_tol_exp": self._tol_exp}):
             if dense:
-                K = _lib.f64(covfunc.getCovMatrix(x=x, mode="train"))
-                rc = lib.pgp_laplace_fit_dense(ctx, _lib.ptr(K), lik, _lib.ptr(likhyp), nlik, _lib.ptr(m), _lib.ptr(dm), nm, want,
-                                               int(warm), _lib.ptr(alpha), _lib.ptr(sW), _lib.ptr(nlZ), _lib.ptr(g),
-                                               C.byref(steps), _lib.ptr(trace), C.byref(fh))
+                K = _lib.f64(covfunc.getCovMatrix(x=p.x, mode="train"))
+                rc = lib.pgp_laplace_fit_dense(ctx, _lib.ptr(K), *tail)
                 del K
             else:
-                rc = lib.pgp_laplace_fit(ctx, kind, _lib.ptr(hyp), nc, int(para), int(flags), lik, _lib.ptr(likhyp), nlik,
-                                         _lib.ptr(m), _lib.ptr(dm), nm, want, int(warm), _lib.ptr(alpha), _lib.ptr(sW),
-                                         _lib.ptr(nlZ), _lib.ptr(g), C.byref(steps), _lib.ptr(trace), C.byref(fh))
-        finally:
-            if self._tol_exp is not None:
-                lib.pgp_set_option(ctx, b"laplace_tol_exp", 6)
+                rc = lib.pgp_laplace_fit(ctx, p.kind, _lib.ptr(p.hyp), nc, int(p.para), int(p.flags), *tail)
         if rc == _lib.ERR_LAPLACE_WNEG:
             raise NotImplementedError("pygps_amd: Laplace met W < 0 (the reference's LU branch is not restated)")
         _lib.check(rc, "pgp_laplace_fit_dense" if dense else "pgp_laplace_fit")
         self.newton_steps = steps.value
         self.last_steps = trace[:self.newton_steps].copy()
         self.last_alpha = alpha.reshape(n, 1)                   # inf.py:513
-        post = postStruct()
-        post.alpha = alpha.reshape(n, 1).copy()
-        post.sW = sW.reshape(n, 1)
-        post.L = DeviceFactor(fh, n, dev, _lib.current_slot())
-        if dense:
-            post.L.dense = True                                 # predict hands the cross-covariance block in (GP._latent)
+        post = _posterior(alpha.reshape(n, 1).copy(), sW.reshape(n, 1), DeviceFactor(fh, n, p.dev, _lib.current_slot()), dense)
+        dnlZ = None
         if nargout > 2:
-            dnlZ = dnlZStruct(meanfunc, covfunc, likfunc)
-            dnlZ.mean = [np.float64(v) for v in g[:nm]]
-            if dense:
-                gh = np.zeros(1)
-                dnlZ.cov = []
-                for h in range(len(hyp)):                       # one derivative matrix at a time (inf.py:536-541)
-                    dK = _lib.f64(covfunc.getDerMatrix(x=x, mode="train", der=h))
-                    _lib.check(lib.pgp_dense_grad_term(ctx, _lib.ptr(dK), n, 0.0, _lib.ptr(gh)), "pgp_dense_grad_term")
-                    dnlZ.cov.append(np.float64(gh[0]))
-            else:
-                dnlZ.cov = [np.float64(v) for v in g[nm:nm + nc]]
-            dnlZ.lik = [np.float64(v) for v in g[nm + nc:nm + nc + nlik]]
-            return post, np.float64(nlZ[0]), dnlZ
-        return post, np.float64(nlZ[0])
+            cov = _dense_cov_grads(lib, ctx, covfunc, p.x, n, 0.0) if dense else None
+            dnlZ = _dnlZ(meanfunc, covfunc, likfunc, g, nm, nc, nlik, cov=cov)
+        return _returns(nargout, post, np.float64(nlZ[0]), dnlZ, always_nlZ=True)
 
 
 class FITCPosterior(object):
@@ -672,6 +645,24 @@ class FITCPosterior(object):
         return self                                      # the device object is immutable; share it
 
 
+def _fitc_inputs(device, meanfunc, covfunc, x, y, nargout, not_fitc):
+    """The FITC engines' checks (``not_fitc`` is raised unless covfunc is a FITC covariance) and inputs: beside ``_prepare``'s,
+    xu (nu, D), nu and dxu -- the (nu, D) output of the gradient w.r.t. the inducing inputs, or None where it is not asked for."""
+    if not isinstance(covfunc, _cov.FITCOfKernel):
+        raise not_fitc
+    _cov.refuse_pre(covfunc.covfunc, "the FITC approximation (fitc(u) of a precomputed matrix has no meaning)")
+    _cov.refuse_dot(covfunc.covfunc, "the FITC approximation")
+    if covfunc.learn_inducing:
+        covfunc._check_learn_inducing()
+    p = _prepare(device, meanfunc, covfunc, x, y, dense_ok=False, reserve=False, inner=True)
+    p.xu = _lib.f64(covfunc.inducingInput)
+    if p.xu.shape[1] != p.D:
+        raise Exception('Dimensionality of inducing inputs must match training inputs')
+    p.nu = p.xu.shape[0]
+    p.dxu = np.zeros((p.nu, p.D)) if (covfunc.learn_inducing and nargout > 2) else None
+    return p
+
+
 class FITC_Exact(Inference):
     """FITC approximation to the posterior GP (Core/inf.py:386-455): exact inference with
     Kt = Q + diag(K - Q), Q = Ku' inv(Kuu + snu2 I) Ku, snu2 = sn2 / 1e6.  One device call (csrc/fitc.hip)."""
@@ -683,56 +674,30 @@ class FITC_Exact(Inference):
     def evaluate(self, meanfunc, covfunc, likfunc, x, y, nargout=1):
         if not isinstance(likfunc, _lik.Gauss):
             raise Exception('Exact inference only possible with Gaussian likelihood')
-        if not isinstance(covfunc, _cov.FITCOfKernel):
-            raise Exception('Only covFITC supported.')
-        _cov.refuse_pre(covfunc.covfunc, "the FITC approximation (fitc(u) of a precomputed matrix has no meaning)")
-        _cov.refuse_dot(covfunc.covfunc, "the FITC approximation")
-        if covfunc.learn_inducing:
-            covfunc._check_learn_inducing()
-        dev = _lib.default_device() if self.device is None else self.device
-        kind, para, flags = _device_kernel(covfunc.covfunc, _lib.ctx(dev))
-        x = _lib.f64(x)
-        n, D = x.shape
-        xu = _lib.f64(covfunc.inducingInput)
-        if xu.shape[1] != D:
-            raise Exception('Dimensionality of inducing inputs must match training inputs')
-        nu = xu.shape[0]
-        dxu = np.zeros((nu, D)) if (covfunc.learn_inducing and nargout > 2) else None
-        y = _lib.f64(y).reshape(n)
-        _Resident.ensure(x, y, dev)
-        m, dm, nm = _mean_inputs(meanfunc, x)
-        hyp = _lib.f64(np.asarray(covfunc.hyp, dtype=float))
-        nc = len(hyp)
+        p = _fitc_inputs(self.device, meanfunc, covfunc, x, y, nargout, Exception('Only covFITC supported.'))
+        n, nm, nu, nc = p.n, p.nm, p.nu, len(p.hyp)
         log_sn = float(likfunc.hyp[0])
         alpha = np.empty(nu)
         Lm = np.empty((nu, nu))
         nlZ = np.zeros(1)
         g = np.zeros(nm + nc + 1)
         fh = C.c_void_p()
-        args = (_lib.ctx(dev), kind, _lib.ptr(hyp), nc, int(para), int(flags), log_sn, _lib.ptr(xu), nu,
-                _lib.ptr(m), _lib.ptr(dm), nm, int(min(max(nargout, 1), 3)), _lib.ptr(alpha),
+        args = (p.ctx, p.kind, _lib.ptr(p.hyp), nc, int(p.para), int(p.flags), log_sn, _lib.ptr(p.xu), nu,
+                _lib.ptr(p.m), _lib.ptr(p.dm), nm, _want(nargout), _lib.ptr(alpha),
                 _lib.ptr(Lm), _lib.ptr(nlZ), _lib.ptr(g), C.byref(fh))
-        if dxu is None:
-            rc = _lib.load().pgp_fitc_fit(*args)
+        if p.dxu is None:
+            rc = p.lib.pgp_fitc_fit(*args)
         else:
-            rc = _lib.load().pgp_fitc_fit_xu(*(args + (_lib.ptr(dxu),)))
+            rc = p.lib.pgp_fitc_fit_xu(*(args + (_lib.ptr(p.dxu),)))
         _lib.check(rc, "pgp_fitc_fit")
-        post = postStruct()
-        post.alpha = alpha.reshape(nu, 1)
-        post.L = Lm                                       # Sigma - inv(Kuu): dense, not triangular (inf.py:424)
-        post.sW = np.ones((n, 1)) / np.sqrt(np.exp(2 * log_sn))
-        post.fitc = FITCPosterior(fh, dev, _lib.current_slot())
-        if nargout > 1:
-            nlz = np.float64(nlZ[0])
-            if nargout > 2:
-                dnlZ = dnlZStruct(meanfunc, covfunc, likfunc)
-                dnlZ.mean = [np.float64(v) for v in g[:nm]]
-                dnlZ.cov = [np.float64(v) for v in g[nm:nm + nc]]
-                dnlZ.lik = [np.float64(g[nm + nc])]
-                dnlZ.xu = dxu
-                return post, nlz, dnlZ
-            return post, nlz
-        return post
+        # post.L = Sigma - inv(Kuu): dense, not triangular (inf.py:424)
+        post = _posterior(alpha.reshape(nu, 1), np.ones((n, 1)) / np.sqrt(np.exp(2 * log_sn)), Lm)
+        post.fitc = FITCPosterior(fh, p.dev, _lib.current_slot())
+        dnlZ = None
+        if nargout > 2:
+            dnlZ = _dnlZ(meanfunc, covfunc, likfunc, g, nm, nc, 1)
+            dnlZ.xu = p.dxu
+        return _returns(nargout, post, np.float64(nlZ[0]), dnlZ)
 
 
 class FITC_EP(Inference):
@@ -759,33 +724,11 @@ class FITC_EP(Inference):
         self._tol_exp = None            # private: sweep tolerance 10^-_tol_exp instead of the reference's 1e-4 (gradient checks)
 
     def evaluate(self, meanfunc, covfunc, likfunc, x, y, nargout=1):
-        if not isinstance(covfunc, _cov.FITCOfKernel):
-            raise NotImplementedError("pygps_amd: FITC_EP needs a FITC covariance (covfunc.fitc(u)); only covFITC is supported")
-        _cov.refuse_pre(covfunc.covfunc, "the FITC approximation (fitc(u) of a precomputed matrix has no meaning)")
-        _cov.refuse_dot(covfunc.covfunc, "the FITC approximation")
-        if isinstance(likfunc, _lik.Laplace):
-            lik, likhyp = _lib.LIK_LAPLACE, _lib.f64(np.asarray(likfunc.hyp, dtype=float).reshape(-1))
-        elif isinstance(likfunc, _lik.Erf):
-            lik, likhyp = _lib.LIK_ERF, None
-        else:
-            raise NotImplementedError("pygps_amd: FITC_EP runs on the device for lik.Erf and lik.Laplace only (no CPU fallback)")
-        nlik = 0 if likhyp is None else 1
-        if covfunc.learn_inducing:
-            covfunc._check_learn_inducing()
-        dev = _lib.default_device() if self.device is None else self.device
-        kind, para, flags = _device_kernel(covfunc.covfunc, _lib.ctx(dev))
-        x = _lib.f64(x)
-        n, D = x.shape
-        xu = _lib.f64(covfunc.inducingInput)
-        if xu.shape[1] != D:
-            raise Exception('Dimensionality of inducing inputs must match training inputs')
-        nu = xu.shape[0]
-        dxu = np.zeros((nu, D)) if (covfunc.learn_inducing and nargout > 2) else None
-        y = _lib.f64(y).reshape(n)
-        _Resident.ensure(x, y, dev)
-        m, dm, nm = _mean_inputs(meanfunc, x)
-        hyp = _lib.f64(np.asarray(covfunc.hyp, dtype=float))
-        nc = len(hyp)
+        lik, likhyp, nlik = _lik_args(likfunc, (_lik.Laplace, _lik.Erf),
+                                      "pygps_amd: FITC_EP runs on the device for lik.Erf and lik.Laplace only (no CPU fallback)")
+        p = _fitc_inputs(self.device, meanfunc, covfunc, x, y, nargout, NotImplementedError(
+            "pygps_amd: FITC_EP needs a FITC covariance (covfunc.fitc(u)); only covFITC is supported"))
+        n, nm, nu, nc = p.n, p.nm, p.nu, len(p.hyp)
         warm = (self.last_ttau is not None and self.last_tnu is not None
                 and np.asarray(self.last_ttau).size == n and np.asarray(self.last_tnu).size == n)
         ttau = _lib.f64(np.asarray(self.last_ttau, dtype=float)).reshape(n).copy() if warm else np.zeros(n)
@@ -796,40 +739,26 @@ class FITC_EP(Inference):
         g = np.zeros(nm + nc + nlik)
         sweeps = C.c_int()
         fh = C.c_void_p()
-        lib, ctx = _lib.load(), _lib.ctx(dev)
-        if self._tol_exp is not None:
-            _lib.check(lib.pgp_set_option(ctx, b"ep_tol_exp", int(self._tol_exp)), "pgp_set_option")
-            _lib.check(lib.pgp_set_option(ctx, b"ep_max_sweep", 1000), "pgp_set_option")
-        try:
-            args = (ctx, kind, _lib.ptr(hyp), nc, int(para), int(flags), lik,
-                    _lib.ptr(likhyp) if nlik else None, nlik, int(bool(self.reference_compat)),
-                    _lib.ptr(xu), nu, _lib.ptr(m), _lib.ptr(dm), nm, int(min(max(nargout, 1), 3)),
+        with _options(p.lib, p.ctx, _ep_options(self._tol_exp)):
+            args = (p.ctx, p.kind, _lib.ptr(p.hyp), nc, int(p.para), int(p.flags), lik, _lib.ptr(likhyp), nlik,
+                    int(bool(self.reference_compat)), _lib.ptr(p.xu), nu, _lib.ptr(p.m), _lib.ptr(p.dm), nm, _want(nargout),
                     int(warm), _lib.ptr(ttau), _lib.ptr(tnu), _lib.ptr(alpha), _lib.ptr(Lm),
                     _lib.ptr(nlZ), _lib.ptr(g), C.byref(sweeps), C.byref(fh))
-            rc = lib.pgp_fitc_ep_fit_lik(*args) if dxu is None else lib.pgp_fitc_ep_fit_lik_xu(*(args + (_lib.ptr(dxu),)))
-        finally:
-            if self._tol_exp is not None:
-                lib.pgp_set_option(ctx, b"ep_tol_exp", 4)
-                lib.pgp_set_option(ctx, b"ep_max_sweep", 10)
+            if p.dxu is None:
+                rc = p.lib.pgp_fitc_ep_fit_lik(*args)
+            else:
+                rc = p.lib.pgp_fitc_ep_fit_lik_xu(*(args + (_lib.ptr(p.dxu),)))
         _lib.check(rc, "pgp_fitc_ep_fit_lik")
         self.sweeps = sweeps.value
         if self.sweeps == 10:
             logging.getLogger(__name__).warning("maximum number of sweeps reached in function infEP")
         self.last_ttau = ttau.reshape(n, 1)                     # inf.py:899-900
         self.last_tnu = tnu.reshape(n, 1)
-        post = postStruct()
-        post.alpha = alpha.reshape(nu, 1)
-        post.L = Lm                                       # -R0'V inv(Kt + diag(1/ttau)) V'R0: dense, not triangular (inf.py:908)
-        post.sW = np.sqrt(ttau).reshape(n, 1)             # inf.py:902
-        post.fitc = FITCPosterior(fh, dev, _lib.current_slot())
-        if nargout > 1:
-            nlz = np.float64(nlZ[0])
-            if nargout > 2:
-                dnlZ = dnlZStruct(meanfunc, covfunc, likfunc)
-                dnlZ.mean = [np.float64(v) for v in g[:nm]]
-                dnlZ.cov = [np.float64(v) for v in g[nm:nm + nc]]
-                dnlZ.lik = [np.float64(v) for v in g[nm + nc:]]
-                dnlZ.xu = dxu
-                return post, nlz, dnlZ
-            return post, nlz
-        return post
+        # post.L = -R0'V inv(Kt + diag(1/ttau)) V'R0: dense, not triangular (inf.py:908); post.sW: inf.py:902
+        post = _posterior(alpha.reshape(nu, 1), np.sqrt(ttau).reshape(n, 1), Lm)
+        post.fitc = FITCPosterior(fh, p.dev, _lib.current_slot())
+        dnlZ = None
+        if nargout > 2:
+            dnlZ = _dnlZ(meanfunc, covfunc, likfunc, g, nm, nc, nlik)
+            dnlZ.xu = p.dxu
+        return _returns(nargout, post, np.float64(nlZ[0]), dnlZ)

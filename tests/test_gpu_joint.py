@@ -47,6 +47,7 @@ import pytest
 
 import joint_ref_ld as J
 import predict_ref_ld as P
+from pool_state import pool_state as _pool_state
 
 pytestmark = pytest.mark.gpu
 
@@ -303,13 +304,6 @@ def test_sample_prior(lib, kernel, ns):
 
 
 # ---- 6: refusals and statuses ----------------------------------------------------------------------------------------------------
-def _pool_state(lib, handle=None):
-    from pygps_amd import _lib
-    out = (C.c_int64 * 9)()        # [7], [8]: scratch-pool bytes / buffers that are out (taken, not yet given back)
-    assert lib.pgp_test_pool_state(_lib.ctx(), handle, out) == 0
-    return list(out)
-
-
 def test_refusals(lib):
     import pygps_amd as pyGPs
     m, xs, idx = _case("rbf300", 129)

@@ -327,3 +327,91 @@ def test_thread_pools_follow_the_cpu_quota(monkeypatch, tmp_path):
     if _threads._LIMIT is not None:                     # (leave this test process as it was)
         _threads._LIMIT.restore_original_limits()
         _threads._LIMIT = None
+
+
+# ---- the helpers the inference engines share (pygps_amd/inf.py) ------------------------------------------------------------
+@pytest.mark.parametrize("nm,nc,nlik", [(0, 2, 1), (2, 3, 0), (1, 0, 1)])
+def test_dnlZ_helper_splits_g_as_the_engines_did_inline(nm, nc, nlik):
+    import pygps_amd as pyGPs
+    from pygps_amd import inf
+    mean = pyGPs.mean.Zero() if nm == 0 else (pyGPs.mean.Const(0.5) if nm == 1 else pyGPs.mean.Linear(D=2))
+    k = pyGPs.cov.RBF() if nc == 2 else pyGPs.cov.RBFard(D=2)
+    likf = pyGPs.lik.Gauss() if nlik else pyGPs.lik.Erf()
+    g = np.arange(1.0, nm + nc + nlik + 2.0) * 0.37              # one entry more than is read, as EP's and Laplace's g have
+    d = inf._dnlZ(mean, k, likf, g, nm, nc, nlik)
+    old = inf.dnlZStruct(mean, k, likf)                           # the inline code of the engines before the helper
+    old.mean = [np.float64(v) for v in g[:nm]]
+    old.cov = [np.float64(v) for v in g[nm:nm + nc]]
+    old.lik = [np.float64(g[nm + nc])] if nlik else []
+    assert (d.mean, d.cov, d.lik) == (old.mean, old.cov, old.lik) and d.xu is None
+    assert (len(d.mean), len(d.cov), len(d.lik)) == (nm, nc, nlik)
+    assert all(type(v) is np.float64 for v in d.mean + d.cov + d.lik)
+    # the dense route: the covariance part comes from elsewhere and g holds [mean | lik]
+    dd = inf._dnlZ(mean, k, likf, g, nm, 0, nlik, cov=["c"])
+    assert dd.cov == ["c"] and dd.mean == old.mean and dd.lik == [np.float64(v) for v in g[nm:nm + nlik]]
+
+
+def test_lik_helper_codes_and_each_engines_refusal():
+    from pygps_amd import _lib, inf, lik
+    ep = (lik.Laplace, lik.Erf)
+    assert inf._lik_args(lik.Erf(), ep, "no") == (_lib.LIK_ERF, None, 0)
+    code, hyp, nlik = inf._lik_args(lik.Laplace(-0.3), ep, "no")
+    assert (code, nlik) == (_lib.LIK_LAPLACE, 1) and hyp.dtype == np.float64 and hyp.tolist() == [-0.3]
+    code, hyp, nlik = inf.Laplace()._lik_args(lik.Gauss(0.2))
+    assert (code, nlik) == (_lib.LIK_GAUSS, 1) and hyp.tolist() == [0.2]
+    assert inf.Laplace()._lik_args(lik.Erf()) == (_lib.LIK_ERF, None, 0)
+    x, y = np.zeros((4, 2)), np.ones((4, 1))
+    import pygps_amd as pyGPs
+    zero, rbf = pyGPs.mean.Zero(), pyGPs.cov.RBF()
+    with pytest.raises(NotImplementedError, match="^pygps_amd: EP runs on the device for lik.Erf and lik.Laplace only"):
+        inf.EP().evaluate(zero, rbf, lik.Gauss(), x, y, 1)
+    with pytest.raises(NotImplementedError, match="^pygps_amd: Laplace runs on the device for lik.Erf and lik.Gauss only"):
+        inf.Laplace().evaluate(zero, rbf, lik.Laplace(), x, y, 1)
+    with pytest.raises(NotImplementedError, match="^pygps_amd: FITC_EP runs on the device for lik.Erf and lik.Laplace only"):
+        inf.FITC_EP().evaluate(zero, rbf.fitc(x[:2]), lik.Gauss(), x, y, 1)
+
+
+class _RecordingLib(object):
+    def __init__(self, fail=None):
+        self.calls, self.fail = [], fail
+
+    def pgp_set_option(self, ctx, name, value):
+        self.calls.append((name, value))
+        return -5 if name == self.fail and value != {b"ep_tol_exp": 4, b"ep_max_sweep": 10, b"laplace_tol_exp": 6}[name] else 0
+
+
+def test_option_context_restores_the_defaults_raised_or_not():
+    from pygps_amd import inf
+    sets = [(b"ep_tol_exp", 9), (b"ep_max_sweep", 1000)]
+    back = [(b"ep_tol_exp", 4), (b"ep_max_sweep", 10)]
+    lib = _RecordingLib()
+    with inf._options(lib, None, inf._ep_options(9)):
+        assert lib.calls == sets
+    assert lib.calls == sets + back
+    lib = _RecordingLib()
+    with pytest.raises(KeyError):
+        with inf._options(lib, None, inf._ep_options(9)):
+            raise KeyError("inside")
+    assert lib.calls == sets + back
+    lib = _RecordingLib()
+    with pytest.raises(ZeroDivisionError):
+        with inf._options(lib, None, {b"laplace_tol_exp": 11}):
+            1 / 0
+    assert lib.calls == [(b"laplace_tol_exp", 11), (b"laplace_tol_exp", 6)]
+    lib = _RecordingLib()                                       # no private tolerance: nothing is set, nothing restored
+    with inf._options(lib, None, inf._ep_options(None)):
+        pass
+    assert lib.calls == []
+    lib, ran = _RecordingLib(fail=b"ep_max_sweep"), []          # a setting that fails raises through _lib.check; the block does not run
+    with pytest.raises(Exception, match="pgp_set_option"):
+        with inf._options(lib, None, inf._ep_options(9)):
+            ran.append(1)
+    assert not ran and lib.calls == sets + back
+
+
+def test_return_ladder_of_both_conventions():
+    from pygps_amd import inf
+    assert inf._returns(1, "p", 1.0, None) == "p" and inf._returns(0, "p", 1.0, None) == "p"
+    assert inf._returns(2, "p", 1.0, None) == ("p", 1.0) and inf._returns(3, "p", 1.0, "d") == ("p", 1.0, "d")
+    assert inf._returns(1, "p", 1.0, None, always_nlZ=True) == ("p", 1.0)      # EP and Laplace
+    assert inf._returns(3, "p", 1.0, "d", always_nlZ=True) == ("p", 1.0, "d")
